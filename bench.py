@@ -129,6 +129,33 @@ def cpu_baseline(workload, budget_clips=8, steps=16):
                       f"{torch.get_num_threads()} threads of {avail} visible cores (oracle/: frontend + augment + fwd/bwd + AdamW)"}
 
 
+DUMP_MAX_ELEMENTS = 3 << 20      # per array: 12 MiB of float32, at most 4 arrays + the loss; a larger state is dumped as a fixed, seeded sample
+
+
+def dump_outputs(trainer, loss, out_dir, max_elements=DUMP_MAX_ELEMENTS):
+    """--dump-outputs: what a caller of trainer.step holds after the last timed step, as float32 .npy files under out_dir: the step's
+    loss and the state the step updated -- the online network (parameters and BatchNorm buffers), the predictor and the EMA target
+    (byol), the loss's BatchNorm buffers.  A module's floating-point state_dict entries are flattened in key order (the reference's
+    key names, independent of the flat-buffer layout) and concatenated; past max_elements a sample at sorted indices drawn from a
+    generator seeded 0 stands in for the whole, so two builds run with the same arguments are compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(()).cpu().numpy()}
+    for name, module in (("online_state", trainer.online), ("predictor_state", trainer.predictor), ("target_state", trainer.target),
+                         ("criterion_state", trainer.criterion)):
+        if module is None:
+            continue
+        vals = [v.detach().reshape(-1).float() for v in module.state_dict().values() if v.is_floating_point()]
+        flat = torch.cat(vals)
+        if flat.numel() > max_elements:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), max_elements, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays[name] = flat.cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: a.shape for name, a in arrays.items()}
+
+
 def profiler_in_environment():
     """The marker of a rocprofiler tool library injected into this process (rocprofv3 sets these for the program it starts), or None."""
     for k in ("ROCP_TOOL_LIBRARIES", "ROCPROFILER_REGISTER_FORCE_LOAD", "ROCPROF_OUTPUT_PATH", "ROCPROF_OUTPUT_FILE_NAME"):
@@ -208,7 +235,7 @@ def dry_run(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="vit_base_bt_10s", choices=sorted(WORKLOADS))
     ap.add_argument("--batch_per_gpu", type=int, default=None)
@@ -231,7 +258,11 @@ def main():
     ap.add_argument("--dry_run", action="store_true", help="rendezvous only: initialise the process group exactly as a real run does, "
                     "exchange one tensor, print the launch / environment fields of the JSON line with value null -- no GPU is touched "
                     "(CPU rehearsal of the N > 1 launch: SA_DIST_BACKEND=gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (loss, "
+                    "updated model state; seeded samples of large states) as DIR/<name>.npy, float32 (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if "RANK" not in os.environ and (args.gpus > 1 or args.dry_launch or os.environ.get("SA_BENCH_SELF_LAUNCH") == "1"):
         sys.exit(self_launch(args))
     if args.dry_run:
@@ -332,6 +363,9 @@ def main():
     trainer.assert_finite()                                        # the step's device-side finite-loss counter, read once here
     note(f"timed region done: {args.steps} steps in {dt:.3f}s")
     loss_val = float(loss)
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(trainer, loss, args.dump_outputs)
+        note(f"outputs of timed step {args.steps} written to {args.dump_outputs}: {shapes}")
     # roofline pass, OUTSIDE the timed region: a few eager steps of the same workload with HIP events (on the launch stream) around every
     # GEMM launch and around the HBM-bound frontend / augmentation / LayerNorm / AdamW launches
     psteps = max(args.profile_steps, 1)

@@ -95,3 +95,47 @@ def test_self_launch_is_refused_from_a_profiled_process():
         assert r.returncode == 3 and "refusing to self-launch" in r.stderr and "starting" not in r.stderr, (marker, r.stderr[-500:])
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry_launch"], env=dict(_env(), ROCPROF_OUTPUT_PATH="/tmp/x"), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "launch" in r.stdout
+
+
+def test_steps_below_one_are_refused():
+    """--steps sets the number of timed steps: zero steps time nothing and are refused before any GPU call."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0"], env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_writes_the_step_state_and_a_fixed_sample(tmp_path):
+    """--dump-outputs on CPU stand-ins for the trainer's modules: float32 files, the whole state in state_dict key order while it fits,
+    a sample at fixed sorted indices past the cap (identical from call to call), and a bound of 64 MB on everything written."""
+    import numpy as np
+    import torch
+    from types import SimpleNamespace
+    bench = _bench_module()
+    torch.manual_seed(0)
+    online = torch.nn.Sequential(torch.nn.Linear(32, 16), torch.nn.BatchNorm1d(16))
+    crit = torch.nn.BatchNorm1d(4, affine=False)
+    tr = SimpleNamespace(online=online, predictor=None, target=None, criterion=crit)
+    loss = torch.tensor(1.25)
+    shapes = bench.dump_outputs(tr, loss, str(tmp_path / "a"))
+    assert sorted(shapes) == ["criterion_state", "loss", "online_state"]
+    full = np.concatenate([v.detach().reshape(-1).float().numpy() for v in online.state_dict().values() if v.is_floating_point()])
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in shapes}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].shape == () and float(got["loss"]) == 1.25
+    np.testing.assert_array_equal(got["online_state"], full)
+    np.testing.assert_array_equal(got["criterion_state"], np.concatenate([np.zeros(4), np.ones(4)]).astype(np.float32))
+    cap = 100
+    bench.dump_outputs(tr, loss, str(tmp_path / "b"), max_elements=cap)
+    bench.dump_outputs(tr, loss, str(tmp_path / "c"), max_elements=cap)
+    b, c = np.load(tmp_path / "b" / "online_state.npy"), np.load(tmp_path / "c" / "online_state.npy")
+    idx = np.sort(np.random.default_rng(0).choice(full.size, cap, replace=False))
+    np.testing.assert_array_equal(b, full[idx])
+    np.testing.assert_array_equal(b, c)
+    assert 4 * bench.DUMP_MAX_ELEMENTS * 4 + 4 <= 64 << 20           # at most four sampled states and the loss, float32
