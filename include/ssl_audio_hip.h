@@ -142,8 +142,10 @@ int64_t sa_layernorm_bwd_workspace_bytes(int32_t M, int32_t D);
  * lse: fp32 [sequences*H][N] log-sum-exp of the scaled scores (saved for backward; may be NULL in fwd).
  * bwd writes dqkv in the same packed layout as qkv (every element of the [rows][3C] block is written).
  * n_query (0 = all N): only the first n_query tokens of each sequence act as queries (forward writes only those rows
- * of `out`; backward treats dout of the other rows as zero) -- the last encoder block needs the CLS row only, because
- * MaskedAutoencoderViT.forward returns x[:, 0] (models/mae.py:463). */
+ * of `out` and `lse`; backward gives them no upstream gradient) -- the last encoder block needs the CLS row only, because
+ * MaskedAutoencoderViT.forward returns x[:, 0] (models/mae.py:463).  The backward still reads the other rows of `out` and
+ * `dout` and multiplies them by zero: their values do not matter, but they must be finite (a NaN or Inf there reaches dK / dV).
+ * scale: positive and finite (the forward's row max is taken on the unscaled scores). */
 int sa_attention_fwd(const void* qkv, int64_t rows, int64_t ld, int32_t C, int32_t H, int32_t N, int32_t n_query, float scale,
                      void* out, int64_t ldo, float* lse, void* stream);
 int sa_attention_bwd(const void* qkv, int64_t rows, int64_t ld, int32_t C, int32_t H, int32_t N, int32_t n_query, float scale,

@@ -514,8 +514,10 @@ __global__ __launch_bounds__(64 * NW_BWD, NMAX == 256 ? 4 : 2) void attn_bwd_ker
 
 }  // namespace
 
-static int attn_check(const char* who, const void* qkv, int64_t rows, int64_t ld, int C, int H, int N) {
+static int attn_check(const char* who, const void* qkv, int64_t rows, int64_t ld, int C, int H, int N, float scale) {
   SA_CHECK_ARG(qkv && rows > 0, "%s: null/empty input", who);
+  // the forward takes the row max on raw scores and folds the scale into the exponent: only a positive finite scale keeps that the max
+  SA_CHECK_ARG(scale > 0.f && scale < INFINITY, "%s: scale %g must be positive and finite", who, (double)scale);
   SA_CHECK_ARG(H > 0 && C == H * HD, "%s: head_dim must be %d (C=%d, H=%d)", who, HD, C, H);
   SA_CHECK_ARG(N > 0 && N <= NMAX_ALL, "%s: sequence length %d outside [1, %d]", who, N, NMAX_ALL);
   SA_CHECK_ARG(rows % N == 0, "%s: rows=%lld not a multiple of N=%d", who, (long long)rows, N);
@@ -527,7 +529,7 @@ static int attn_check(const char* who, const void* qkv, int64_t rows, int64_t ld
 extern "C" int sa_attention_fwd(const void* qkv, int64_t rows, int64_t ld, int32_t C, int32_t H, int32_t N, int32_t n_query, float scale,
                                 void* out, int64_t ldo, float* lse, void* stream) {
   if (n_query <= 0 || n_query > N) n_query = N;
-  if (attn_check("sa_attention_fwd", qkv, rows, ld, C, H, N)) return 1;
+  if (attn_check("sa_attention_fwd", qkv, rows, ld, C, H, N, scale)) return 1;
   SA_CHECK_ARG(out && ldo >= C && ldo % 4 == 0, "sa_attention_fwd: bad output");
   const int S = (int)(rows / N);
   if (N <= 256) {
@@ -580,7 +582,7 @@ static int attn_bwd_grid(int units, int per_cu) {
 extern "C" int sa_attention_bwd(const void* qkv, int64_t rows, int64_t ld, int32_t C, int32_t H, int32_t N, int32_t n_query, float scale,
                                 const void* out, const void* dout, int64_t ldo, const float* lse, void* dqkv, void* stream) {
   if (n_query <= 0 || n_query > N) n_query = N;
-  if (attn_check("sa_attention_bwd", qkv, rows, ld, C, H, N)) return 1;
+  if (attn_check("sa_attention_bwd", qkv, rows, ld, C, H, N, scale)) return 1;
   SA_CHECK_ARG(out && dout && lse && dqkv && ldo >= C && ldo % 8 == 0, "sa_attention_bwd: bad args");
   SA_CHECK_ARG(((uintptr_t)dout & 15) == 0 && ((uintptr_t)out & 15) == 0, "sa_attention_bwd: out/dout must be 16-byte aligned");
   const int S = (int)(rows / N);

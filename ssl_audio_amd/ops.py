@@ -366,6 +366,9 @@ def attention_fwd(qkv, H, N, scale, out, lse=None, n_query=0):
 
 
 def attention_bwd(qkv, H, N, scale, out, dout, lse, dqkv, n_query=0):
+    """dqkv (every element of its [rows, 3C] block) = the gradient of the attention forward, from its out and lse.  With n_query, rows
+    >= n_query of each sequence are not queries: their out and dout rows get no gradient through, but must be finite (they are read and
+    multiplied by zero -- a NaN there would reach dK / dV; the engine zero-fills them)."""
     rows, w, ld = _rows(_req(qkv, BF16, "qkv"), "qkv")
     Cdim = w // 3
     if _rows(dqkv, "dqkv")[2] != ld or _rows(dout, "dout")[2] != _rows(out, "out")[2]:

@@ -202,11 +202,19 @@ def test_c_abi_rejects_bad_arguments_before_touching_the_gpu():
     P = C.c_void_p
     null = P(0)
     one = P(8)          # non-null, never dereferenced: every call below fails validation first
+    al = P(16)          # the same, 16-byte aligned
     cases = {
         "sa_layernorm_fwd": lambda: h.sa_layernorm_fwd(null, 0, null, null, null, null, 0, null, null, 4, 768, 1e-6, null),
         "sa_layernorm_fwd(D)": lambda: h.sa_layernorm_fwd(one, 770, one, one, one, null, 770, null, null, 4, 770, 1e-6, null),
         "sa_layernorm_bwd(ws)": lambda: h.sa_layernorm_bwd(one, 1, 768, one, 768, one, one, one, null, 0, one, null, 768, one, null, null, null, 4, 768, null),
         "sa_attention_fwd": lambda: h.sa_attention_fwd(one, 8, 2304, 768, 12, 300, 0, 0.125, one, 768, null, null),
+        # a scale that is not positive and finite (every other argument valid): the forward's row max is taken on unscaled scores
+        "sa_attention_fwd(scale -0.125)": lambda: h.sa_attention_fwd(al, 498, 2304, 768, 12, 249, 0, -0.125, al, 768, null, null),
+        "sa_attention_fwd(scale 0)": lambda: h.sa_attention_fwd(al, 498, 2304, 768, 12, 249, 0, 0.0, al, 768, null, null),
+        "sa_attention_fwd(scale nan)": lambda: h.sa_attention_fwd(al, 498, 2304, 768, 12, 249, 1, float("nan"), al, 768, null, null),
+        "sa_attention_fwd(scale inf)": lambda: h.sa_attention_fwd(al, 498, 2304, 768, 12, 249, 0, float("inf"), al, 768, null, null),
+        "sa_attention_bwd(scale -0.125)": lambda: h.sa_attention_bwd(al, 498, 2304, 768, 12, 249, 0, -0.125, al, al, 768, al, al, null),
+        "sa_attention_bwd(scale nan)": lambda: h.sa_attention_bwd(al, 498, 2304, 768, 12, 249, 0, float("nan"), al, al, 768, al, al, null),
         "sa_gather_rows": lambda: h.sa_gather_rows(one, 0, 0, one, 4, one, 0, 0, 2, 6, null),
         "sa_mae_unshuffle_fwd": lambda: h.sa_mae_unshuffle_fwd(one, 9, one, one, one, 2, 8, 64, one, null),
         "sa_mae_recon_loss_fwd": lambda: h.sa_mae_recon_loss_fwd(one, 10, 1, one, one, 2, 60, 96, 16, 16, 0, one, one, one, null),
@@ -217,6 +225,7 @@ def test_c_abi_rejects_bad_arguments_before_touching_the_gpu():
         msg = h.sa_last_error().decode()
         assert rc != 0, name
         assert name.split("(")[0] in msg, (name, msg)
+        assert "(scale" not in name or "scale" in msg, (name, msg)
     g = _lib.SaGemmArgs()
     g.A, g.B, g.M, g.N, g.K, g.lda, g.ldb, g.split_k = 8, 8, 16, 16, 16, 12, 16, 1        # lda not a multiple of 8 elements
     g.out_f32, g.ldo_f32, g.a_kmajor, g.b_kmajor, g.alpha = 8, 16, 1, 1, 1.0
