@@ -57,8 +57,9 @@ typedef struct SaGemmArgs {
   int32_t split_k;              /* >= 1.  > 1: K is split over workgroups and partial tiles are atomically
                                    ADDED into out_f32 (caller zeroes / owns accumulation); only alpha is applied */
   int32_t accumulate;           /* split_k == 1 only: out_f32 += v instead of = v */
-  int32_t tile256;              /* split_k > 1 only: 1 = the 256 x 256 tile (one workgroup per CU) instead of 128 x 128; 2 = the 192 x 192
-                                   streaming kernel (both operands k-strided; three K-steps in LDS, for outputs a few hundred wide) */
+  int32_t tile256;              /* split_k > 1 only, both operands k-strided: 1 = the 256 x 256 streaming kernel (one workgroup per CU)
+                                   instead of 128 x 128; 2 = the 192 x 192 streaming kernel (three K-steps in LDS, for outputs a few
+                                   hundred wide) */
   float* colsum_out;            /* optional [N]: += column sums of the fp32 epilogue result (the bias gradient of the Linear that
                                    produced this GEMM's A operand's gradient, e.g. fc1's bias from the fc2 dgrad: utils of
                                    models/mae.py:155 backward).  Needs split_k == 1, N % 64 == 0 and colsum_ws. */
@@ -68,7 +69,7 @@ typedef struct SaGemmArgs {
                                    out_f32 in slice order: the result is bit-reproducible from run to run (the atomic path is
                                    exact only up to the fp32 rounding of an arbitrary summation order).  Served by the two default
                                    split-K kernels (128 x 128 and tile256) */
-  float* asum_out;              /* optional, the streaming split-K kernels only (both operands k-strided, split_k > 1, tile256 = 2 or 1; also per
+  float* asum_out;              /* optional, the streaming split-K kernels only (split_k > 1 and tile256 = 1 or 2; also per
                                    product of sa_gemm_wgrad_group): asum_out[m] += sum_k A[k][m] for m < M outside [asum_skip_lo, asum_skip_hi)
                                    -- the BIAS gradient of the Linear whose weight gradient this product is (A = dY), taken from the dY tiles the
                                    kernel has in LDS anyway instead of a second pass over dY (sa_colsum_bf16).  The skipped rows: the k third

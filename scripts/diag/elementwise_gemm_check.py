@@ -1,6 +1,6 @@
 """ELEMENTWISE check of the tiled GEMM kernels' compact epilogues at step-sized shapes (norm-relative tests can hide a handful of
 corrupted elements): every output element against an fp64 reference, bound = bf16 / fp32 rounding of that element + accumulation noise.
-Motivation: the store-data hazard found in gemm_wreg.hip (scripts/diag/scan_store_hazard.py lists
+Motivation: the store-data hazard found in gemm_wreg.hip (since removed; scripts/diag/scan_store_hazard.py lists
 the same instruction pattern in the tiled kernels' ISA).   python scripts/diag/elementwise_gemm_check.py [reps]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

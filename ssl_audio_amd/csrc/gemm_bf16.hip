@@ -149,227 +149,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(const GemmParams p) {
 }
 
 // =====================================================================================================
-// 256 x 256 x 64 tile, 512 threads = 8 waves (2 x 4), each wave 128 x 64 (8 x 4 MFMA tiles, 128 accumulator VGPRs),
-// one workgroup per CU (2 x 64 KiB LDS buffers).  Why: a CU pulls L2-resident operands at only ~30 B/clk, so the
-// 128^2 kernel (32 KiB of operands per 2.1 MFLOP) is bound by that path long before the MFMA pipe; 256^2 halves
-// the bytes per FLOP.  Each operand tile is two of the 128-wide half-tiles above, so staging and fragment reads are
-// the same code.  Per K-tile the wave walks four C-quadrants (A-half0 x B-half0, A0 x B1, A1 x B1, A1 x B0) so only
-// 12 fragment registers sets are live; the next K-tile's 4 half-tiles are requested at the top of the iteration and
-// awaited at its end (one barrier per K-tile).
-template <bool A_KM, bool B_KM, bool SPLIT>
-__global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][A half0 | A half1 | B half0 | B half1]
-  constexpr int BUF = 4 * TILE_BYTES;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wr = wave >> 2, wc = wave & 3;      // wave rows wr*128.., cols wc*64..
-
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-  constexpr int GM = 4;                          // 32 blocks per XCD ~ 4 x 8 tiles in flight
-  const int ntiles = p.tiles_m * p.tiles_n;
-  const int ks_id = SPLIT ? lid / ntiles : 0;    // split-K slice slowest (co-resident workgroups share their K rows in L2)
-  const int tile = lid - ks_id * ntiles;
-  const int group_sz = GM * p.tiles_n;
-  const int grp = tile / group_sz, within = tile - grp * group_sz;
-  const int gm = min(GM, p.tiles_m - grp * GM);
-  const int tm = grp * GM + within % gm, tn = within / gm;
-  const int m0 = tm * 256, n0 = tn * 256;
-
-  const int ksteps_all = (p.K + BK - 1) / BK;
-  const int chunk = (ksteps_all + p.split_k - 1) / p.split_k;
-  const int kt0 = SPLIT ? ks_id * chunk : 0;
-  const int ksteps = SPLIT ? min(ksteps_all - kt0, chunk) : ksteps_all;
-  if (ksteps <= 0) return;
-  constexpr bool HID = !(A_KM && B_KM);    // kernels with a transposing-read operand hide their LDS-DMA from the compiler (lds_dma16)
-  const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.A, p.a_bytes);
-  const __amdgpu_buffer_rsrc_t rb = make_rsrc(p.B, p.b_bytes);
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  auto stage_all = [&](char* buf, int k0) {
-    stage_tile<A_KM, 8, HID>(ra, buf, p.lda, m0, k0, wave, lane);
-    stage_tile<A_KM, 8, HID>(ra, buf + TILE_BYTES, p.lda, m0 + 128, k0, wave, lane);
-    stage_tile<B_KM, 8, HID>(rb, buf + 2 * TILE_BYTES, p.ldb, n0, k0, wave, lane);
-    stage_tile<B_KM, 8, HID>(rb, buf + 3 * TILE_BYTES, p.ldb, n0 + 128, k0, wave, lane);
-  };
-
-  if (p.stagger & 4) { if (wr == 1) __builtin_amdgcn_s_setprio(1); }     // (see gemm256_persist_kernel; not the default here: no gain measured)
-  stage_all(smem, kt0 * BK);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  int cur = 0;
-  for (int kt = 0; kt < ksteps; ++kt) {
-    // the second wave row requests its share of the next K-tile mid-step (see gemm256_persist_kernel).  Only with compiler-visible
-    // requests: there the mid-step position staggered the drain hipcc puts behind them (lds_dma16) between a SIMD's two waves, 12-14 %
-    // on the wgrad shapes; with hidden requests there is no drain and requesting at the top is 3-5 % faster still
-    const bool late = !HID && p.stagger && wr == 1;
-    if (kt + 1 < ksteps && !late) stage_all(smem + (cur ^ 1) * BUF, (kt0 + kt + 1) * BK);
-    const char* ta = smem + cur * BUF + wr * TILE_BYTES;                 // this wave's A half-tile (128 rows)
-    const char* tb = smem + cur * BUF + (2 + (wc >> 1)) * TILE_BYTES;    // this wave's B half-tile
-    const int bcol = (wc & 1) * 64;
-    bf16x8 fa[4][2], fb0[2][2], fb1[2][2];
-    // quadrant (0,0)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) fa[i][ks] = load_frag<A_KM>(ta, i * 16, ks, lane);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) fb0[j][ks] = load_frag<B_KM>(tb, bcol + j * 16, ks, lane);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (SPLIT ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][ks], fb0[j][ks], acc[i][j], 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb0[j][ks], fa[i][ks], acc[i][j], 0, 0, 0));
-    // quadrant (0,1)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) fb1[j][ks] = load_frag<B_KM>(tb, bcol + 32 + j * 16, ks, lane);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][2 + j] = (SPLIT ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][ks], fb1[j][ks], acc[i][2 + j], 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1[j][ks], fa[i][ks], acc[i][2 + j], 0, 0, 0));
-    if (kt + 1 < ksteps && late) stage_all(smem + (cur ^ 1) * BUF, (kt0 + kt + 1) * BK);
-    // quadrant (1,1)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) fa[i][ks] = load_frag<A_KM>(ta, 64 + i * 16, ks, lane);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[4 + i][2 + j] = (SPLIT ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][ks], fb1[j][ks], acc[4 + i][2 + j], 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1[j][ks], fa[i][ks], acc[4 + i][2 + j], 0, 0, 0));
-    // quadrant (1,0)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[4 + i][j] = (SPLIT ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][ks], fb0[j][ks], acc[4 + i][j], 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb0[j][ks], fa[i][ks], acc[4 + i][j], 0, 0, 0));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cur ^= 1;
-  }
-
-  const int g = lane >> 4, c = lane & 15;
-  if constexpr (SPLIT) {
-    // split-K: lane owns rows 4g + r of one column -> 64-byte row segments per atomic instruction
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wc * 64 + j * 16 + c;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + wr * 128 + i * 16 + 4 * g + r;
-          if (m < p.M && n < p.N) {
-            if (p.split_ws) p.split_ws[((int64_t)ks_id * p.M + m) * p.N + n] = p.alpha * acc[i][j][r];
-            else atomicAdd(p.out_f32 + (int64_t)m * p.ldo_f32 + n, p.alpha * acc[i][j][r]);
-          }
-        }
-      }
-    return;
-  }
-  // ---------------------------------------------------------------- epilogue (lane: one row m, 4 consecutive n)
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int m = m0 + wr * 128 + i * 16 + c;
-    if (m >= p.M) continue;
-    const int64_t orow = p.row_group > 0 ? (int64_t)m + m / p.row_group + 1 : (int64_t)m;
-    const int64_t rrow = p.res_mod > 0 ? (int64_t)(m % p.res_mod) : (int64_t)m;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wc * 64 + j * 16 + 4 * g;
-      if (n + 3 >= p.N) {
-        for (int r = 0; r < 4 && n + r < p.N; ++r) {
-          float x = acc[i][j][r] * p.alpha;
-          if (p.bias) x += p.bias[n + r];
-          if (p.act == 1 || p.act == 3) {
-            if (p.aux_out) p.aux_out[(int64_t)m * p.ldaux + n + r] = f2bf(p.act == 3 ? dgelu_f(x) : x);
-            x = gelu_f(x);
-          } else if (p.act == 2 || p.act == 4) {
-            const float h = bf2f(p.aux_in[(int64_t)m * p.ldaux + n + r]);
-            x *= p.act == 4 ? h : dgelu_f(h);
-          }
-          if (p.residual) x += p.residual[rrow * p.ldr + n + r];
-          if (p.out_f32) {
-            float* o = p.out_f32 + orow * p.ldo_f32 + n + r;
-            *o = p.accumulate ? *o + x : x;
-          }
-          if (p.out_bf16) p.out_bf16[orow * p.ldo_bf16 + n + r] = f2bf(x);
-        }
-        continue;
-      }
-      float v[4] = {acc[i][j][0] * p.alpha, acc[i][j][1] * p.alpha, acc[i][j][2] * p.alpha, acc[i][j][3] * p.alpha};
-      if (p.bias) {
-        const float4 b = *reinterpret_cast<const float4*>(p.bias + n);
-        v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
-      }
-      if (p.act == 1 || p.act == 3) {
-        if (p.aux_out) {
-          bf16x4 h = {f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
-          if (p.act == 3) h = bf16x4{f2bf(dgelu_f(v[0])), f2bf(dgelu_f(v[1])), f2bf(dgelu_f(v[2])), f2bf(dgelu_f(v[3]))};
-          *reinterpret_cast<bf16x4*>(p.aux_out + (int64_t)m * p.ldaux + n) = h;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = gelu_f(v[r]);
-      } else if (p.act == 2 || p.act == 4) {
-        const bf16x4 h = *reinterpret_cast<const bf16x4*>(p.aux_in + (int64_t)m * p.ldaux + n);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= p.act == 4 ? bf2f(h[r]) : dgelu_f(bf2f(h[r]));
-      }
-      if (p.residual) {
-        const float4 rv = *reinterpret_cast<const float4*>(p.residual + rrow * p.ldr + n);
-        v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
-      }
-      if (p.out_f32) {
-        float* o = p.out_f32 + orow * p.ldo_f32 + n;
-        if (p.accumulate) {
-          const float4 old = *reinterpret_cast<const float4*>(o);
-          v[0] += old.x; v[1] += old.y; v[2] += old.z; v[3] += old.w;
-        }
-        *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-      }
-      if (p.out_bf16) {
-        bf16x4 h = {f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
-        *reinterpret_cast<bf16x4*>(p.out_bf16 + orow * p.ldo_bf16 + n) = h;
-      }
-    }
-  }
-}
-
-template <bool A_KM, bool B_KM, bool SPLIT = false>
-int launch256(GemmParams p, hipStream_t stream) {
-  p.tiles_m = (p.M + 255) / 256;
-  p.tiles_n = (p.N + 255) / 256;
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256_kernel<A_KM, B_KM, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              8 * TILE_BYTES);
-    configured = true;
-  }
-  hipLaunchKernelGGL((gemm256_kernel<A_KM, B_KM, SPLIT>), dim3(p.tiles_m * p.tiles_n * (SPLIT ? p.split_k : 1)), dim3(512), 8 * TILE_BYTES,
-                     stream, p);
-  SA_LAUNCH_CHECK("sa_gemm_bf16(256)");
-  return 0;
-}
-
-// =====================================================================================================
+// 256 x 256 x 64 tiles, 512 threads = 8 waves (2 x 4), each wave 128 x 64 (8 x 4 MFMA tiles, 128 accumulator VGPRs), one workgroup per
+// CU.  Why: a CU pulls L2-resident operands at only ~30 B/clk, so the 128^2 kernel (32 KiB of operands per 2.1 MFLOP) is bound by that
+// path long before the MFMA pipe; 256^2 halves the bytes per FLOP.  Each operand tile is two of the 128-wide half-tiles above, so staging
+// and fragment reads are the same code.  Per K-tile the wave walks four C-quadrants (A-half0 x B-half0, A0 x B1, A1 x B1, A1 x B0) so
+// only 12 fragment register sets are live.
+//
 // Persistent 256 x 256 x 64 kernel (forward / dgrad): one workgroup per CU walks tiles lid, lid + grid, ...  With a single
 // resident workgroup nothing else hides the pipeline fill and the store tail of a 12-iteration (K = 768) tile, so the
 // kernel hides them itself: the next tile's first K-tile is requested during the last K-iteration and lands while the
@@ -413,7 +198,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_persist_kernel(const GemmParam
   // the younger ones' MFMA segments take twice as long (cycle stamps of scripts/microbench/gemm_dephase_prof.hip: 2 300 - 2 800 against
   // 1 300 cycles); MI355X_MICROARCH.md, "Two waves per SIMD", item 4
   // -- measured (scripts/bench_gemm.py, A/B/A/B on one box): qkv forward 251-259 -> 240-241 us, fc1 forward 401-412 -> 384-386,
-  // fc2 dgrad 378-380 -> 357-360, proj dgrad 76-79 -> 71.5; default on (SA_GEMM_STAGGER bit 1)
+  // fc2 dgrad 378-380 -> 357-360, proj dgrad 76-79 -> 71.5; default on (STAGGER bit 1)
   if (p.stagger & 2) { if (wr == 1) __builtin_amdgcn_s_setprio(1); }
   int m0, n0;
   coords(t, m0, n0);
@@ -595,7 +380,7 @@ int launch256_persist(GemmParams p, hipStream_t stream) {
 
 
 // =====================================================================================================
-// Persistent 256 x 256 x 64 kernel over a FIVE-slot ring of 32 KiB half-stages ("mode 8"; forward / dgrad and split-K wgrad).
+// Persistent 256 x 256 x 64 kernel over a FIVE-slot ring of 32 KiB half-stages ("mode 8"; forward / dgrad).
 // Measured with scripts/microbench/dma_bw.hip: one workgroup per CU streams operand tiles L2 -> LDS at ~23 B/clk/CU with one
 // 64 KiB stage in flight and ~34 B/clk/CU with two -- the 256^2 tile needs 32 B/clk/CU at MFMA peak, so bytes in flight are
 // the limiter, and 160 KiB of LDS cannot hold three 64 KiB stages.  Splitting a stage into its A half and B half lets the
@@ -605,7 +390,7 @@ int launch256_persist(GemmParams p, hipStream_t stream) {
 //   into the two slots step g has just finished reading.
 // Requests past the end of the stream go out of range (zero fill, no traffic) so the outstanding count stays exact; the
 // K-step right after an epilogue waits vmcnt(0) because stores / atomics sit between the loads in the counter.
-template <bool A_KM, bool B_KM, bool SPLIT, int EPI = 0>
+template <bool A_KM, bool B_KM, int EPI = 0>
 __global__ __launch_bounds__(512, 2) void gemm256_ring_kernel(const GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int HALF = 2 * TILE_BYTES;               // 32 KiB: [rows 0..127 | rows 128..255] of one operand
@@ -617,22 +402,18 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring_kernel(const GemmParams p
   const int bid = blockIdx.x;
   const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
   const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-  const int ntiles = p.tiles_m * p.tiles_n;
-  const int nunits = ntiles * (SPLIT ? p.split_k : 1);
+  const int nunits = p.tiles_m * p.tiles_n;
   const int GM = p.gm256;
   const int group_sz = GM * p.tiles_n;
   const int ksteps_all = (p.K + BK - 1) / BK;
-  const int chunk = SPLIT ? (ksteps_all + p.split_k - 1) / p.split_k : ksteps_all;
-  // unit -> (m0, n0, first K-step, number of K-steps); split-K slice slowest so co-resident workgroups share K rows in L2
-  auto unit = [&](int u, int& m0, int& n0, int& kt0, int& nk) {
-    const int ks_id = SPLIT ? u / ntiles : 0;
-    const int t = u - ks_id * ntiles;
+  // unit (output tile) -> (m0, n0, first K-step, number of K-steps)
+  auto unit = [&](int t, int& m0, int& n0, int& kt0, int& nk) {
     const int grp = t / group_sz, within = t - grp * group_sz;
     const int gm = min(GM, p.tiles_m - grp * GM);
     m0 = (grp * GM + within % gm) * 256;
     n0 = (within / gm) * 256;
-    kt0 = ks_id * chunk;
-    nk = min(ksteps_all - kt0, chunk);
+    kt0 = 0;
+    nk = ksteps_all;
   };
   constexpr bool HID = !(A_KM && B_KM);    // kernels with a transposing-read operand hide their LDS-DMA from the compiler (lds_dma16)
   const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.A, p.a_bytes);
@@ -691,7 +472,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring_kernel(const GemmParams p
   bool pending = false;
   bool fresh = false;
   const int bcol = (wc & 1) * 64;
-#define SA_MM(FA, FB, ACC) (SPLIT ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA, FB, ACC, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_bf16(FB, FA, ACC, 0, 0, 0))
+#define SA_MM(FA, FB, ACC) __builtin_amdgcn_mfma_f32_16x16x32_bf16(FB, FA, ACC, 0, 0, 0)
   while (true) {
     f32x4 acc[8][4];
 #pragma unroll
@@ -786,40 +567,25 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring_kernel(const GemmParams p
       ca = ca >= 3 ? ca - 3 : ca + 2;
       cb = cb >= 3 ? cb - 3 : cb + 2;
     }
-    if constexpr (SPLIT) {
-      const int g = lane >> 4, c = lane & 15;           // lane owns rows 4g + r of one column -> 64-byte row segments per atomic
+    char* wl = smem + (wave < 4 ? ea * HALF + wave * 8192 : eb * HALF + (wave - 4) * 8192);
+    if constexpr (EPI == 4 || EPI == 5) {
+      // the wave's whole aux_in block (128 rows x 64 columns) is requested before the first store: a load issued after a store
+      // sits behind it in the in-order vmcnt queue, and waiting for it would drain the first half's stores (an HBM round trip)
+      const int nb = n0 + wc * 64;
+      uint4 auxv[16];
 #pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = n0 + wc * 64 + j * 16 + c;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int m = m0 + wr * 128 + i * 16 + 4 * g + r;
-            if (m < p.M && n < p.N) atomicAdd(p.out_f32 + (int64_t)m * p.ldo_f32 + n, p.alpha * acc[i][j][r]);
-          }
-        }
-    } else {
-      char* wl = smem + (wave < 4 ? ea * HALF + wave * 8192 : eb * HALF + (wave - 4) * 8192);
-      if constexpr (EPI == 4 || EPI == 5) {
-        // the wave's whole aux_in block (128 rows x 64 columns) is requested before the first store: a load issued after a store
-        // sits behind it in the in-order vmcnt queue, and waiting for it would drain the first half's stores (an HBM round trip)
-        const int nb = n0 + wc * 64;
-        uint4 auxv[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int m = m0 + wr * 128 + q * 8 + (lane >> 3);
-          auxv[q] = (m < p.M && nb < p.N) ? *reinterpret_cast<const uint4*>(p.aux_in + (int64_t)m * p.ldaux + nb + (lane & 7) * 8) : make_uint4(0u, 0u, 0u, 0u);
-        }
-        wave_epilogue_compact<true, EPI>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[0]), m0 + wr * 128, nb, wl, lane, nullptr, nullptr, &auxv[0]);
-        wave_epilogue_compact<true, EPI>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[4]), m0 + wr * 128 + 64, nb, wl, lane, nullptr, nullptr, &auxv[8]);
-      } else if constexpr (EPI != 0) {
-        wave_epilogue_compact<true, EPI>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[0]), m0 + wr * 128, n0 + wc * 64, wl, lane);
-        wave_epilogue_compact<true, EPI>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[4]), m0 + wr * 128 + 64, n0 + wc * 64, wl, lane);
-      } else {
-        wave_epilogue_64x64<true>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[0]), m0 + wr * 128, n0 + wc * 64, wl, lane);
-        wave_epilogue_64x64<true>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[4]), m0 + wr * 128 + 64, n0 + wc * 64, wl, lane);
+      for (int q = 0; q < 16; ++q) {
+        const int m = m0 + wr * 128 + q * 8 + (lane >> 3);
+        auxv[q] = (m < p.M && nb < p.N) ? *reinterpret_cast<const uint4*>(p.aux_in + (int64_t)m * p.ldaux + nb + (lane & 7) * 8) : make_uint4(0u, 0u, 0u, 0u);
       }
+      wave_epilogue_compact<true, EPI>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[0]), m0 + wr * 128, nb, wl, lane, nullptr, nullptr, &auxv[0]);
+      wave_epilogue_compact<true, EPI>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[4]), m0 + wr * 128 + 64, nb, wl, lane, nullptr, nullptr, &auxv[8]);
+    } else if constexpr (EPI != 0) {
+      wave_epilogue_compact<true, EPI>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[0]), m0 + wr * 128, n0 + wc * 64, wl, lane);
+      wave_epilogue_compact<true, EPI>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[4]), m0 + wr * 128 + 64, n0 + wc * 64, wl, lane);
+    } else {
+      wave_epilogue_64x64<true>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[0]), m0 + wr * 128, n0 + wc * 64, wl, lane);
+      wave_epilogue_64x64<true>(p, reinterpret_cast<f32x4(&)[4][4]>(acc[4]), m0 + wr * 128 + 64, n0 + wc * 64, wl, lane);
     }
     u += nwg;
     if (u >= nunits) break;
@@ -833,17 +599,11 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring_kernel(const GemmParams p
 #undef SA_MM
 }
 
-template <bool A_KM, bool B_KM, bool SPLIT>
+template <bool A_KM, bool B_KM>
 int launch256_ring(GemmParams p, hipStream_t stream) {
   p.tiles_m = (p.M + 255) / 256;
   p.tiles_n = (p.N + 255) / 256;
-  if (SPLIT) {                                          // no empty K slices: the kernel's two cursors must agree on the unit list
-    const int ksteps_all = (p.K + BK - 1) / BK;
-    const int chunk = (ksteps_all + p.split_k - 1) / p.split_k;
-    p.split_k = (ksteps_all + chunk - 1) / chunk;
-  } else {
-    p.split_k = 1;
-  }
+  p.split_k = 1;
   static int slots = 0;
   if (slots == 0) {
     int dev = 0;
@@ -852,35 +612,35 @@ int launch256_ring(GemmParams p, hipStream_t stream) {
       sa_set_error("sa_gemm_bf16: cannot query the device");
       return 2;
     }
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256_ring_kernel<A_KM, B_KM, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256_ring_kernel<A_KM, B_KM>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             10 * TILE_BYTES) != hipSuccess) {
       sa_set_error("sa_gemm_bf16: 160 KiB of LDS per workgroup refused");
       return 2;
     }
     slots = prop.multiProcessorCount;
   }
-  const int nunits = p.tiles_m * p.tiles_n * p.split_k;
+  const int nunits = p.tiles_m * p.tiles_n;
   const dim3 grid(nunits < budget_slots(slots) ? nunits : budget_slots(slots));
-  if constexpr (A_KM && !B_KM && !SPLIT) {  // the dgrad layout gets kernels specialised on the compact epilogues 1 and 4
+  if constexpr (A_KM && !B_KM) {  // the dgrad layout gets kernels specialised on the compact epilogues 1 and 4
 #define SA_EPI_CASE(E)                                                                                                     \
   case E: {                                                                                                                \
     static bool cfg = false;                                                                                               \
     if (!cfg) {                                                                                                            \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256_ring_kernel<true, false, false, E>),                   \
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256_ring_kernel<true, false, E>),                   \
                               hipFuncAttributeMaxDynamicSharedMemorySize, 10 * TILE_BYTES) != hipSuccess) {                \
         sa_set_error("sa_gemm_bf16: 160 KiB of LDS per workgroup refused");                                                \
         return 2;                                                                                                          \
       }                                                                                                                    \
       cfg = true;                                                                                                          \
     }                                                                                                                      \
-    hipLaunchKernelGGL((gemm256_ring_kernel<true, false, false, E>), grid, dim3(512), 10 * TILE_BYTES, stream, p);          \
+    hipLaunchKernelGGL((gemm256_ring_kernel<true, false, E>), grid, dim3(512), 10 * TILE_BYTES, stream, p);          \
     SA_LAUNCH_CHECK("sa_gemm_bf16(256 ring, compact epilogue)");                                                           \
     return 0;                                                                                                              \
   }
     switch (p.epi_kind) { SA_EPI_CASE(1) SA_EPI_CASE(4) SA_EPI_CASE(5) default: break; }
 #undef SA_EPI_CASE
   }
-  hipLaunchKernelGGL((gemm256_ring_kernel<A_KM, B_KM, SPLIT>), grid, dim3(512), 10 * TILE_BYTES, stream, p);
+  hipLaunchKernelGGL((gemm256_ring_kernel<A_KM, B_KM>), grid, dim3(512), 10 * TILE_BYTES, stream, p);
   SA_LAUNCH_CHECK("sa_gemm_bf16(256 ring)");
   return 0;
 }
@@ -1118,7 +878,55 @@ extern "C" int sa_gemm_bf16(const SaGemmArgs* a, void* stream_) {
 }
 
 namespace {
+// Settled tuning values.  Each was an environment knob while it was measured (scripts/bench_gemm.py); GemmParams keeps the ones the
+// kernels read as fields, so the kernels did not change when the knobs went.
+constexpr int GM_128 = 8;             // row-panels per tile group, 128^2 kernel: the ~64 blocks resident on an XCD cover 8 x 8 tiles of one L2
+constexpr int GM_256 = 4;             // the same for the 256^2 kernels: 32 blocks per XCD ~ 4 x 8 tiles in flight
+constexpr int STAGGER = 3;            // persistent 256^2 kernel: wave row 1 requests mid-step (bit 0: 2-4 % on the forward shapes) and runs
+                                      // at priority 1 (bit 1: qkv forward 251-259 -> 240-241 us, fc2 dgrad 378-380 -> 357-360)
+constexpr int RING_PHASE = 1;         // ring kernel: requests phased by wave row, 3-8 % over the uniform trickle on the dgrad shapes
+constexpr int NT_STORE = 1;           // non-temporal bf16 stores: without them +8 % launch time on the qkv / fc1 forward and fc2 dgrad shapes
+constexpr int BIG_MIN_N = 192;        // narrowest output on the 256^2 kernels: d = 192 (ViT-T) pads 25 % of a tile and is still 10-30 %
+                                      // faster than the 128^2 kernel with its general epilogue
+constexpr int PHASE_MIN_K_BIAS = 1536;  // phased kernel on the bias -> bf16 epilogue from this K on: 266 vs 285 us at K = 3072, 197 vs 211
+                                        // at 2304, a tie at 768
+
+enum class GemmKernel { Tile128, Persist256, Ring256, Phase256, Stream192, Stream256 };
+
+// Which kernel a launch runs: the whole policy in one place.  `forced` is SA_GEMM_TILE ('1', '6', '8' or 'A'; 0: none), an A/B switch
+// that applies to split_k == 1 only.
+GemmKernel select_kernel(const SaGemmArgs& a, int epi_kind, char forced) {
+  // split-K (weight gradients): the 128^2 kernel, or with tile256 a streaming kernel of gemm_stream.hip (k-strided operands)
+  if (a.split_k > 1) return a.tile256 == 2 ? GemmKernel::Stream192 : a.tile256 ? GemmKernel::Stream256 : GemmKernel::Tile128;
+  // large dense problems go to the 256 x 256 kernels (half the operand bytes per FLOP through the CU's L2 path); small / ragged
+  // problems to the plain 128 x 128 kernel
+  const bool big = a.M >= 1024 && a.N >= BIG_MIN_N && (int64_t)((a.M + 255) / 256) * ((a.N + 255) / 256) >= 128;
+  // the ring (mode 8) measured 8-13 % faster than the persistent kernel (mode 6) on the dgrad layout (NN: k-strided weight) and equal on
+  // the forward layout (NT); the persistent kernel measured 12 % faster than the 128^2 kernel over the ViT-B forward + dgrad shapes
+  const GemmKernel wide = (a.a_kmajor && !a.b_kmajor) ? GemmKernel::Ring256 : GemmKernel::Persist256;
+  // what the phased kernel (mode A, gemm_phase.hip) is built for
+  const bool phase_covers = a.a_kmajor && a.K >= 2 * BK && (epi_kind == 1 || epi_kind == 3 || epi_kind == 5 || epi_kind == 6);
+  switch (forced) {
+    case '1': return GemmKernel::Tile128;
+    case '6': return GemmKernel::Persist256;
+    case '8': return GemmKernel::Ring256;
+    case 'A':
+      if (phase_covers) return GemmKernel::Phase256;
+      if (a.K >= 2 * BK && epi_kind != 0 && epi_kind != 2 && epi_kind != 4) return wide;   // (kind 8, k-strided A: whatever the size)
+      return big ? wide : GemmKernel::Tile128;
+    default: break;
+  }
+  if (!big) return GemmKernel::Tile128;
+  // the phased kernel measured faster than the persistent one on the forward layout with the bias + residual -> fp32 epilogue (proj 150
+  // vs 163 us, fc2 305 vs 343), on bias -> bf16 once the reduction is long (PHASE_MIN_K_BIAS) or the output narrow (one column tile) from
+  // K = 512 on (ViT-T's fc1 / qkv data gradients 59 -> 51 us, 43 -> 41 us), and equal or slower elsewhere
+  const bool phased = a.b_kmajor && phase_covers &&
+                      (epi_kind == 3 || (epi_kind == 1 && (a.K >= PHASE_MIN_K_BIAS || (a.N <= 256 && a.K >= 512))));
+  return phased ? GemmKernel::Phase256 : wide;
+}
+
 int gemm_dispatch(const SaGemmArgs* a, hipStream_t stream) {
+  // ---- 1. arguments
   SA_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "sa_gemm_bf16: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
   SA_CHECK_ARG(a->A && a->B, "sa_gemm_bf16: null operand");
   SA_CHECK_ARG(a->out_f32 || a->out_bf16, "sa_gemm_bf16: no output");
@@ -1138,9 +946,6 @@ int gemm_dispatch(const SaGemmArgs* a, hipStream_t stream) {
   if (a->residual) SA_CHECK_ARG(a->ldr % 4 == 0 && ((uintptr_t)a->residual & 15) == 0, "sa_gemm_bf16: residual must be 16-byte aligned rows");
   if (a->bias) SA_CHECK_ARG(((uintptr_t)a->bias & 15) == 0, "sa_gemm_bf16: bias must be 16-byte aligned");
   if (a->aux_in || a->aux_out) SA_CHECK_ARG(a->ldaux % 4 == 0, "sa_gemm_bf16: ldaux must be a multiple of 4");
-
-  GemmParams p;
-  p.A = (const char*)a->A; p.B = (const char*)a->B;
   // extents in bytes: last row only spans its valid elements, so anything past it is out of range (zero fill)
   const int64_t a_rows = a->a_kmajor ? a->M : a->K, a_cols = a->a_kmajor ? a->K : a->M;
   const int64_t b_rows = a->b_kmajor ? a->N : a->K, b_cols = a->b_kmajor ? a->K : a->N;
@@ -1148,6 +953,19 @@ int gemm_dispatch(const SaGemmArgs* a, hipStream_t stream) {
   const int64_t lim = (int64_t)1 << 32;
   SA_CHECK_ARG((a_rows + 2 * BM) * a->lda * 2 < lim && (b_rows + 2 * BM) * a->ldb * 2 < lim,
                "sa_gemm_bf16: operand larger than the 4 GiB buffer-descriptor range");
+  if (a->asum_out) {
+    SA_CHECK_ARG(a->split_k > 1 && !a->a_kmajor && !a->b_kmajor && (a->tile256 == 1 || a->tile256 == 2),
+                 "sa_gemm_bf16: asum_out is served by the streaming split-K kernels only (k-strided operands, split_k > 1, tile256 = 2 or 1)");
+    SA_CHECK_ARG((a->asum_ws != nullptr) == (a->splitk_ws != nullptr), "sa_gemm_bf16: asum_ws goes with splitk_ws (both or neither)");
+    SA_CHECK_ARG(a->asum_skip_lo >= 0 && a->asum_skip_hi >= a->asum_skip_lo, "sa_gemm_bf16: bad asum_skip range");
+  }
+  static const char* force = getenv("SA_GEMM_TILE");
+  SA_CHECK_ARG(!force || (force[0] && !force[1] && strchr("168A", force[0])),
+               "sa_gemm_bf16: SA_GEMM_TILE=%s: 1 (128^2), 6 (persistent 256^2), 8 (ring 256^2) or A (phased 256^2)", force);
+
+  // ---- 2. kernel parameters
+  GemmParams p;
+  p.A = (const char*)a->A; p.B = (const char*)a->B;
   p.a_bytes = (uint32_t)a_bytes; p.b_bytes = (uint32_t)b_bytes;
   p.lda = (int)a->lda; p.ldb = (int)a->ldb;
   p.M = a->M; p.N = a->N; p.K = a->K; p.alpha = a->alpha;
@@ -1161,24 +979,18 @@ int gemm_dispatch(const SaGemmArgs* a, hipStream_t stream) {
   p.split_ws = a->split_k > 1 ? a->splitk_ws : nullptr;
   p.tile_counter = nullptr;
   p.asum_out = a->asum_out; p.asum_ws = a->asum_ws; p.asum_lo = a->asum_skip_lo; p.asum_hi = a->asum_skip_hi;
-  if (a->asum_out) {
-    static const char* ws256 = getenv("SA_GEMM_WGRAD_STREAM256");
-    const bool stream_path = a->split_k > 1 && !a->a_kmajor && !a->b_kmajor &&
-                             (a->tile256 == 2 || (a->tile256 == 1 && !(ws256 && ws256[0] == '0') && (!a->splitk_ws || a->N % 4 == 0)));
-    SA_CHECK_ARG(stream_path, "sa_gemm_bf16: asum_out is served by the streaming split-K kernels only (k-strided operands, split_k > 1, tile256 = 2 or 1)");
-    SA_CHECK_ARG((a->asum_ws != nullptr) == (a->splitk_ws != nullptr), "sa_gemm_bf16: asum_ws goes with splitk_ws (both or neither)");
-    SA_CHECK_ARG(a->asum_skip_lo >= 0 && a->asum_skip_hi >= a->asum_skip_lo, "sa_gemm_bf16: bad asum_skip range");
-  }
-  static const char* es_env = getenv("SA_GEMM_EPI_COMPACT");
+  p.tiles_m = (a->M + BM - 1) / BM; p.tiles_n = (a->N + BN - 1) / BN;
+  p.gm = GM_128; p.gm256 = GM_256;
+  p.stagger = STAGGER; p.ring_phase = RING_PHASE; p.nt_store = NT_STORE;
+
+  // ---- 3. epilogue classification: which compact epilogue (wave_epilogue_compact) the launch can take, 0: the general one
   p.epi_kind = 0;
   {
-    const bool al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; }(a->out_bf16) && [](const void* q) { return ((uintptr_t)q & 15) == 0; }(a->aux_out) &&
-                      [](const void* q) { return ((uintptr_t)q & 7) == 0; }(a->aux_in);
+    const bool al16 = ((uintptr_t)a->out_bf16 & 15) == 0 && ((uintptr_t)a->aux_out & 15) == 0 && ((uintptr_t)a->aux_in & 7) == 0;
     // the compact epilogues address their bf16 outputs / inputs through buffer descriptors (32-bit byte offsets, the rows of the last
     // tile included): matrices past that range take the general epilogue
-    const int64_t lim32 = (int64_t)1 << 32;
-    const bool desc_ok = (!a->out_bf16 || ((int64_t)a->M + 512) * a->ldo_bf16 * 2 < lim32) && (!(a->aux_in || a->aux_out) || ((int64_t)a->M + 512) * a->ldaux * 2 < lim32);
-    const bool base_ok = !(es_env && es_env[0] == '0') && a->split_k == 1 && a->row_group == 0 && a->res_mod == 0 && !a->accumulate && a->N % 64 == 0 && al16 && desc_ok;
+    const bool desc_ok = (!a->out_bf16 || ((int64_t)a->M + 512) * a->ldo_bf16 * 2 < lim) && (!(a->aux_in || a->aux_out) || ((int64_t)a->M + 512) * a->ldaux * 2 < lim);
+    const bool base_ok = a->split_k == 1 && a->row_group == 0 && a->res_mod == 0 && !a->accumulate && a->N % 64 == 0 && al16 && desc_ok;
     const bool bf16_only = a->out_bf16 && !a->out_f32 && a->ldo_bf16 % 8 == 0 && !a->residual;
     if (base_ok && bf16_only && a->act == 0 && !a->aux_in && !a->aux_out && !a->colsum_out) p.epi_kind = 1;
     else if (base_ok && bf16_only && a->act == 1 && a->aux_out && a->ldaux % 8 == 0 && !a->colsum_out) p.epi_kind = 2;   // (not dispatched: spills)
@@ -1189,111 +1001,33 @@ int gemm_dispatch(const SaGemmArgs* a, hipStream_t stream) {
     else if (base_ok && bf16_only && (a->act == 2 || a->act == 4) && a->aux_in && !a->bias && a->ldaux % 8 == 0 && ((uintptr_t)a->aux_in & 15) == 0)
       p.epi_kind = a->act == 2 ? 4 : 5;
   }
-  static const char* rp_env = getenv("SA_GEMM_RING_PHASE");
-  p.ring_phase = (rp_env && rp_env[0] == '0') ? 0 : 1;   // default on: 3-8 % on the dgrad shapes (SA_GEMM_RING_PHASE=0: uniform trickle)
-  static const char* stg_env = getenv("SA_GEMM_STAGGER");
-  p.stagger = stg_env ? atoi(stg_env) : 3;              // bit 0: late requests of wave row 1; bit 1: priority 1 for wave row 1 in the persistent kernel; bit 2: the same in the split-K 256^2 kernel (experiment)   // default on: measured 2-4 % on the forward shapes, 12-14 % on split-K wgrad (SA_GEMM_STAGGER=0 disables)
-  static const char* gm256_env = getenv("SA_GEMM_GM256");
-  p.gm256 = gm256_env ? atoi(gm256_env) : 4;
-  if (p.gm256 < 1) p.gm256 = 1;
-  static const char* nt_env = getenv("SA_GEMM_NT");
-  p.nt_store = nt_env ? atoi(nt_env) : 1;          // SA_GEMM_NT=0 switches the streaming bf16 stores off (measured: +8 % launch time on
-                                                    // the qkv / fc1 forward and fc2 dgrad shapes; fp32 outputs and read-once loads: no effect)
-  p.tiles_m = (a->M + BM - 1) / BM; p.tiles_n = (a->N + BN - 1) / BN;
-  static const char* gm_env = getenv("SA_GEMM_GM");
-  p.gm = gm_env ? atoi(gm_env) : 8;
-  if (p.gm < 1) p.gm = 1;
 
-  // large dense problems go to the 256 x 256 kernel (half the operand bytes per FLOP through the CU's L2 path)
-  static const char* force = getenv("SA_GEMM_TILE");
-  static const char* bign_env = getenv("SA_GEMM_BIG_N");       // experiment knob: narrowest output that still takes the 256 x 256 kernels
-  const int big_n = bign_env ? atoi(bign_env) : 192;           // d = 192 (ViT-T) outputs: 25 % of a 256-wide tile is padding, still 10-30 % faster
-                                                               // than the 128^2 kernel with its general epilogue (scripts/bench_gemm.py, SA_BENCH_D=192)
-  const bool big = a->split_k == 1 && a->M >= 1024 && a->N >= big_n && (int64_t)((a->M + 255) / 256) * ((a->N + 255) / 256) >= 128;
-  // Measured on the ViT-B shapes (scripts/bench_gemm.py, random operands): the 128^2 kernel (mode 1, two 4-wave
-  // workgroups per CU) beats the 256x128 three-stage (mode 3) and 256^2 (mode 2) variants at K = 768;
-  // those stay selectable through SA_GEMM_TILE for experiments and are parity-tested.
-  // default for large problems: mode 6, the persistent 256 x 256 kernel (measured 12 % faster than mode 1 over the ViT-B
-  // forward + dgrad shapes: scripts/bench_gemm.py); small / ragged problems use the plain 128 x 128 kernel.
-  // mode 8 (five-slot half-stage ring, requests trickled between MFMAs) measured 8-13 % faster than mode 6 on the dgrad (NN,
-  // k-strided weight) shapes and equal on forward (NT): it is the default for NN only.
-  // mode A (phased kernel, gemm_phase.hip): measured faster than mode 6 on the forward layout with the bias + residual -> fp32
-  // epilogue (proj 150 vs 163 us, fc2 305 vs 343 us) and equal or slower elsewhere (scripts/bench_gemm.py): default there only.
-  // ... and on the plain bias -> bf16 epilogue once the reduction is long (K >= 1536: 266 vs 285 us at K = 3072, 197 vs 211 at 2304; a tie at 768).
-  static const char* k1_env = getenv("SA_GEMM_PHASE_K1");      // experiment knob: minimum K for mode A on epilogue kind 1 (0: never)
-  const int k1_min = k1_env ? atoi(k1_env) : 1536;
-  // ... and on narrow outputs (one column tile: N <= 256) from K = 512 on: ViT-T's fc1 / qkv data gradients 59 -> 51 us, 43 -> 41 us
-  const bool nt_phase = a->a_kmajor && a->b_kmajor && a->K >= 2 * BK &&
-                        (p.epi_kind == 3 || (p.epi_kind == 1 && k1_min > 0 && (a->K >= k1_min || (a->N <= 256 && a->K >= 512))));
-  // thin reductions (K = 192: ViT-T) can stream through the weights-in-registers kernel (gemm_wreg.hip).  OPT-IN (SA_GEMM_WREG=1; 2 = and fail
-  // when a K = 192 forward-layout launch is not covered, for the parity test): built in round 5, parity-green, measured equal or slower
-  // than the tiled kernels on every ViT-T shape
-  static const char* wreg_env = getenv("SA_GEMM_WREG");
-  if (!force && wreg_env && (wreg_env[0] == '1' || wreg_env[0] == '2') && a->split_k == 1 && a->a_kmajor && a->b_kmajor && a->K == 192 && a->M >= 4096) {
-    const int rc = p.epi_kind != 0 ? sagemm::launch_wreg(p, stream) : -1;
-    if (rc >= 0) return rc;
-    SA_CHECK_ARG(wreg_env[0] != '2', "sa_gemm_bf16: SA_GEMM_WREG=2 and this K = 192 launch is not covered by the weights-in-registers kernel (N=%d, epilogue kind %d)", a->N, p.epi_kind);
-  }
-  char mode = force ? force[0] : (big ? ((a->a_kmajor && !a->b_kmajor) ? '8' : (nt_phase ? 'A' : '6')) : '1');
-  // mode P (gemm_pair.hip): 128 x 256 tiles, two 4-wave workgroups per CU -- one's epilogue under the other's main loop
-  static const char* pair_env = getenv("SA_GEMM_PAIR");        // experiment knob: list of epilogue kinds that take mode P, e.g. "36"
-  if (!force && big && pair_env && a->a_kmajor && a->b_kmajor && p.epi_kind > 0 && p.epi_kind < 10 && strchr(pair_env, '0' + p.epi_kind)) mode = 'P';
-  if (mode == 'P' && a->split_k == 1) {
-    if (a->a_kmajor && a->b_kmajor && big) {
-      SA_CHECK_ARG((a_rows + 512) * a->lda * 2 < lim && (b_rows + 512) * a->ldb * 2 < lim, "sa_gemm_bf16: operand too large for the 256 tile");
-      const int rc = sagemm::launch_pair(p, stream);
-      if (rc >= 0) return rc;
-    }
-    mode = big ? ((a->a_kmajor && !a->b_kmajor) ? '8' : (nt_phase ? 'A' : '6')) : '1';
-  }
-  if (mode == 'A' && a->split_k == 1 && a->K >= 2 * BK && p.epi_kind != 0 && p.epi_kind != 2 && p.epi_kind != 4) {
-    SA_CHECK_ARG((a_rows + 512) * a->lda * 2 < lim && (b_rows + 512) * a->ldb * 2 < lim, "sa_gemm_bf16: operand too large for the 256 tile");
-    const int rc = sagemm::launch_phase(p, a->a_kmajor, a->b_kmajor, false, stream);
-    if (rc >= 0) return rc;
-    mode = (a->a_kmajor && !a->b_kmajor) ? '8' : '6';
-  } else if (mode == 'A' && a->split_k == 1) {
-    mode = big ? ((a->a_kmajor && !a->b_kmajor) ? '8' : '6') : '1';
-  }
-  if (mode == '8' && a->split_k == 1) {
-    SA_CHECK_ARG((a_rows + 512) * a->lda * 2 < lim && (b_rows + 512) * a->ldb * 2 < lim, "sa_gemm_bf16: operand too large for the 256 tile");
-    if (a->a_kmajor && a->b_kmajor) return launch256_ring<true, true, false>(p, stream);
-    if (a->a_kmajor && !a->b_kmajor) return launch256_ring<true, false, false>(p, stream);
-    if (!a->a_kmajor && a->b_kmajor) return launch256_ring<false, true, false>(p, stream);
-    return launch256_ring<false, false, false>(p, stream);
-  }
-  if (mode == '6' && a->split_k == 1) {
-    SA_CHECK_ARG((a_rows + 512) * a->lda * 2 < lim && (b_rows + 512) * a->ldb * 2 < lim, "sa_gemm_bf16: operand too large for the 256 tile");
-    if (a->a_kmajor && a->b_kmajor) return launch256_persist<true, true>(p, stream);
-    if (a->a_kmajor && !a->b_kmajor) return launch256_persist<true, false>(p, stream);
-    if (!a->a_kmajor && a->b_kmajor) return launch256_persist<false, true>(p, stream);
-    return launch256_persist<false, false>(p, stream);
-  }
-  if (a->split_k > 1 && a->tile256 == 2) {
-    SA_CHECK_ARG(!a->a_kmajor && !a->b_kmajor, "sa_gemm_bf16: tile256 = 2 (the 192 x 192 streaming kernel) takes k-strided operands only");
-    SA_CHECK_ARG((a_rows + 512) * a->lda * 2 < lim && (b_rows + 512) * a->ldb * 2 < lim, "sa_gemm_bf16: operand too large for the 192 tile");
-    return sagemm::launch_stream(p, stream);
-  }
-  if (a->split_k > 1 && a->tile256) {
-    SA_CHECK_ARG((a_rows + 512) * a->lda * 2 < lim && (b_rows + 512) * a->ldb * 2 < lim, "sa_gemm_bf16: operand too large for the 256 tile");
-    // TN (weight gradients): the four-stage ring of gemm_stream.hip, default since round 5 (three 32 KiB stages in flight against one
-    // 64 KiB stage: fc1 / fc2 282 -> 271 us, qkv 247 -> 243, proj 71 -> 75; ViT-B step 40.94 -> 40.27 ms; SA_GEMM_WGRAD_STREAM256=0: the
-    // two-stage kernel below)
-    static const char* wstream = getenv("SA_GEMM_WGRAD_STREAM256");
-    if (!(wstream && wstream[0] == '0') && !a->a_kmajor && !a->b_kmajor && (!p.split_ws || a->N % 4 == 0)) return sagemm::launch_stream256(p, stream);
-    static const char* wphase = getenv("SA_GEMM_WGRAD_PHASE");
-    if (!p.split_ws && wphase && wphase[0] == '1' && !a->a_kmajor && !a->b_kmajor && (a->K + BK - 1) / BK / a->split_k >= 2)
-      return sagemm::launch_phase(p, false, false, true, stream);
-    static const char* wring = getenv("SA_GEMM_WGRAD_RING");
-    if (!p.split_ws && wring && wring[0] == '1') {
-      if (a->a_kmajor && a->b_kmajor) return launch256_ring<true, true, true>(p, stream);
-      if (a->a_kmajor && !a->b_kmajor) return launch256_ring<true, false, true>(p, stream);
-      if (!a->a_kmajor && a->b_kmajor) return launch256_ring<false, true, true>(p, stream);
-      return launch256_ring<false, false, true>(p, stream);
-    }
-    if (a->a_kmajor && a->b_kmajor) return launch256<true, true, true>(p, stream);
-    if (a->a_kmajor && !a->b_kmajor) return launch256<true, false, true>(p, stream);
-    if (!a->a_kmajor && a->b_kmajor) return launch256<false, true, true>(p, stream);
-    return launch256<false, false, true>(p, stream);
+  // ---- 4. kernel selection and launch
+  const GemmKernel kern = select_kernel(*a, p.epi_kind, force ? force[0] : 0);
+  if (kern == GemmKernel::Stream192 || kern == GemmKernel::Stream256)
+    SA_CHECK_ARG(!a->a_kmajor && !a->b_kmajor, "sa_gemm_bf16: tile256 = %d (the %s streaming kernel) takes k-strided operands only",
+                 a->tile256, kern == GemmKernel::Stream192 ? "192 x 192" : "256 x 256");
+  if (kern != GemmKernel::Tile128)      // (the 192 and 256 tiles address up to 512 rows past an operand's last one)
+    SA_CHECK_ARG((a_rows + 512) * a->lda * 2 < lim && (b_rows + 512) * a->ldb * 2 < lim, "sa_gemm_bf16: operand too large for the 192 / 256 tiles");
+  switch (kern) {
+    case GemmKernel::Phase256:
+      return sagemm::launch_phase(p, a->b_kmajor, stream);
+    case GemmKernel::Ring256:
+      if (a->a_kmajor && a->b_kmajor) return launch256_ring<true, true>(p, stream);
+      if (a->a_kmajor && !a->b_kmajor) return launch256_ring<true, false>(p, stream);
+      if (!a->a_kmajor && a->b_kmajor) return launch256_ring<false, true>(p, stream);
+      return launch256_ring<false, false>(p, stream);
+    case GemmKernel::Persist256:
+      if (a->a_kmajor && a->b_kmajor) return launch256_persist<true, true>(p, stream);
+      if (a->a_kmajor && !a->b_kmajor) return launch256_persist<true, false>(p, stream);
+      if (!a->a_kmajor && a->b_kmajor) return launch256_persist<false, true>(p, stream);
+      return launch256_persist<false, false>(p, stream);
+    case GemmKernel::Stream192:
+      return sagemm::launch_stream(p, stream);
+    case GemmKernel::Stream256:
+      return sagemm::launch_stream256(p, stream);
+    case GemmKernel::Tile128:
+      break;
   }
   const bool swap = a->split_k == 1;
   const int sel = (a->a_kmajor ? 4 : 0) | (a->b_kmajor ? 2 : 0) | (swap ? 1 : 0);

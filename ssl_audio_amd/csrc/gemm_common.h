@@ -32,11 +32,11 @@ struct GemmParams {
   int split_k; int accumulate;
   float* split_ws;   // deterministic split-K: slice s stores alpha * partial into split_ws[(s * M + m) * N + n] instead of atomically adding to out_f32
   int tiles_m, tiles_n;
-  int gm;   // row-panels per tile group (L2 locality knob)
+  int gm;            // row-panels per tile group (L2 locality)
   int gm256;         // row-panels per tile group in the 256^2 kernels
-  int stagger;       // persistent 256^2 kernel: wave row 1 requests its LDS-DMA share mid-step
+  int stagger;       // persistent 256^2 kernel: bit 0 = wave row 1 requests its LDS-DMA share mid-step, bit 1 = priority 1 for wave row 1
   int ring_phase;    // ring kernel: requests phased by wave row
-  int epi_kind;      // 1..4: one of the compact epilogues applies (wave_epilogue_compact); 0: general epilogue
+  int epi_kind;      // 1..6, 8: one of the compact epilogues applies (wave_epilogue_compact); 0: general epilogue
   int nt_store;      // bf16 outputs with non-temporal stores
   float* colsum_ws;  // [ceil(M/64)][N] partial column sums of the fp32 epilogue result (bias gradient of the producing Linear), or null
   float* asum_out; float* asum_ws; int asum_lo, asum_hi;   // streaming split-K kernels: column sums of A (see StreamProb)
@@ -48,9 +48,9 @@ struct GemmParams {
 int* next_tile_counter(hipStream_t stream);
 
 
-// gemm_phase.hip: launches the phased kernel for (layout, split) if it covers the problem (compact epilogue kinds 1/3/5/6 or split-K
-// atomics); returns -1 when it does not, 0 on success, 2 on a launch error
-int launch_phase(GemmParams p, bool a_kmajor, bool b_kmajor, bool split, hipStream_t stream);
+// gemm_phase.hip: the phased kernel (A k-major, K >= 2 * BK, split_k == 1, compact epilogue kinds 1 / 3 / 5 / 6: the caller selects it
+// only for those); 0 on success, 2 on a launch error
+int launch_phase(GemmParams p, bool b_kmajor, hipStream_t stream);
 // gemm_stream.hip: the 192 x 192 streaming split-K kernel (both operands k-strided, split_k > 1); 0 on success, 2 on a launch error.
 // One launch serves up to STREAM_MAX_PROBLEMS products over the SAME reduction (a transformer block's four weight gradients): the
 // workgroups -- and with them the fp32 partial tiles the split costs, one per workgroup -- are shared out over all of them.
@@ -75,11 +75,6 @@ int launch_stream(GemmParams p, hipStream_t stream);
 int launch_stream_group(StreamGroup& g, int tile /* 192 or 256 */, hipStream_t stream);
 int launch_stream_reduce(const StreamGroup& g, hipStream_t stream);
 int launch_stream256(GemmParams p, hipStream_t stream);
-// gemm_pair.hip: the 128 x 256 kernel with two workgroups per CU (both operands k-major, compact epilogue kinds 1/3/5/6/8); -1: not covered
-int launch_pair(GemmParams p, hipStream_t stream);
-// gemm_wreg.hip: the weights-in-registers streaming kernel for thin forward-layout products (K = 192, N in {192, 576, 768}, compact
-// epilogue kinds 1 / 3 / 5 / 6 / 8: ViT-T's qkv / proj / fc1 forward, fc2 / proj data gradients); -1: not covered
-int launch_wreg(GemmParams p, hipStream_t stream);
 }  // namespace sagemm
 using sagemm::GemmParams;
 using sagemm::budget_slots;
@@ -302,7 +297,7 @@ __device__ __forceinline__ void staged_store_bf16(const GemmParams& p, f32x4 (&v
     const uint32_t ld2 = (uint32_t)ld * 2u;
     // The row block's offset travels in the PER-LANE offset (one v_add per store), not in the instruction's scalar-offset field: hipcc keeps
     // two wait states between a 16-byte store and a VALU write of its data registers only when that field holds NO register -- with an
-    // SGPR there it assumes the hardware needs none, and on gfx950 that measurably did not hold (gemm_wreg.hip's first build stored a
+    // SGPR there it assumes the hardware needs none, and on gfx950 that measurably did not hold (gemm_wreg.hip's first build -- since removed -- stored a
     // later value for lanes 12 - 15: DESIGN.md section 6, round 5, item 11).  These stores were never caught doing it
     // (tests/test_kernels_gpu.py::test_gemm_elementwise_at_step_shapes), but the ISA had the unprotected pattern at 94 sites
     // (scripts/diag/scan_store_hazard.py); in this form the compiler's own rule pads them.

@@ -1,11 +1,11 @@
 // Phased persistent 256 x 256 x 64 bf16 MFMA GEMM for gfx950 (see the comment above the kernel).  Own translation unit: the
-// kernel family is 12 instantiations of a 250-VGPR kernel and dominates the build time of the library.
+// kernel family is 8 instantiations of a 250-VGPR kernel and dominates the build time of the library.
 #include "gemm_common.h"
 
 namespace {
 
 // =====================================================================================================
-// Phased persistent 256 x 256 x 64 kernel ("mode A"; forward NT, dgrad NN, split-K wgrad TN).
+// Phased persistent 256 x 256 x 64 kernel ("mode A"; forward NT, dgrad NN).
 //
 // Two waves live on every SIMD (waves w and w + 4: wave row 0 = waves 0..3 owns tile rows 0..127, wave row 1 rows 128..255).
 // A K-tile is consumed in FOUR phases, one 64 x 32 quadrant of the wave's 128 x 64 output each; a phase is
@@ -28,7 +28,7 @@ namespace {
 // L segment publishes it to the other waves (read one phase after the wait: cdna_hip_programming.md "Pipelining across
 // barriers").  WAR: every request goes out at least one full barrier interval after the last read of its image completed
 // (the stagger costs row 0 one extra phase for the shared B images; the table above already includes it).
-// The K-tile stream runs across tile (and split-K unit) borders; past its end the requests go out of range (zero fill, no
+// The K-tile stream runs across tile borders; past its end the requests go out of range (zero fill, no
 // traffic, same count).  The epilogue scratch is private to the wave and outside the pipeline, so the stream never stops.
 constexpr int IMG_BYTES = 8192;
 constexpr int PH_BUF = 8 * IMG_BYTES;
@@ -59,7 +59,7 @@ __device__ __forceinline__ bf16x8 ph_frag(const char* img, int sub0, int kstep, 
 __device__ unsigned long long sa_phase_prof[4][8];
 #endif
 
-template <bool A_KM, bool B_KM, bool SPLIT, int EPI>
+template <bool A_KM, bool B_KM, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm256_phase_kernel(const GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -70,21 +70,17 @@ __global__ __launch_bounds__(512, 2) void gemm256_phase_kernel(const GemmParams 
   const int bid = blockIdx.x;
   const int xcd = bid & 7, qq = nwg >> 3, rr = nwg & 7;
   const int lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (bid >> 3);
-  const int ntiles = p.tiles_m * p.tiles_n;
-  const int nunits = ntiles * (SPLIT ? p.split_k : 1);
+  const int nunits = p.tiles_m * p.tiles_n;
   const int GM = p.gm256;
   const int group_sz = GM * p.tiles_n;
   const int ksteps_all = (p.K + BK - 1) / BK;
-  const int chunk = SPLIT ? (ksteps_all + p.split_k - 1) / p.split_k : ksteps_all;
-  auto unit = [&](int u, int& m0, int& n0, int& kt0, int& nk) {
-    const int ks_id = SPLIT ? u / ntiles : 0;
-    const int t = u - ks_id * ntiles;
+  auto unit = [&](int t, int& m0, int& n0, int& kt0, int& nk) {         // unit (output tile) -> (m0, n0, first K-step, number of K-steps)
     const int grp = t / group_sz, within = t - grp * group_sz;
     const int gm = min(GM, p.tiles_m - grp * GM);
     m0 = (grp * GM + within % gm) * 256;
     n0 = (within / gm) * 256;
-    kt0 = ks_id * chunk;
-    nk = min(ksteps_all - kt0, chunk);
+    kt0 = 0;
+    nk = ksteps_all;
   };
   const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.A, p.a_bytes);
   const __amdgpu_buffer_rsrc_t rb = make_rsrc(p.B, p.b_bytes);
@@ -184,7 +180,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_phase_kernel(const GemmParams 
 #else
 #define PH_T(k)
 #endif
-#define SA_MM(FA, FB, ACC) (SPLIT ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(FA, FB, ACC, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_bf16(FB, FA, ACC, 0, 0, 0))
+#define SA_MM(FA, FB, ACC) __builtin_amdgcn_mfma_f32_16x16x32_bf16(FB, FA, ACC, 0, 0, 0)
 #define SA_L_END()                                             \
   PH_T(0)                                                      \
   if (fresh) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(10 + EPI_STORES) : "memory");   \
@@ -212,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_phase_kernel(const GemmParams 
   // vmcnt counts stores too, in issue order: right after an epilogue the counted wait would first drain the tile's stores
   // (an HBM round trip) although everything the next phases read was requested BEFORE them.  For five phases after the epilogue
   // of a FULL tile (its store count is then exact) the wait leaves those stores outstanding as well.
-  constexpr int EPI_STORES = SPLIT ? 0 : (EPI == 1 ? 16 : (EPI == 3 || EPI == 6) ? 32 : 0);
+  constexpr int EPI_STORES = EPI == 1 ? 16 : (EPI == 3 || EPI == 6) ? 32 : 0;
   bool after_full = false;                                   // the previous unit of this workgroup stored a full 256 x 256 tile
   int sidx = 0;                                              // stream index of the K-tile being consumed (buffer = sidx & 1)
   while (true) {
@@ -271,44 +267,29 @@ __global__ __launch_bounds__(512, 2) void gemm256_phase_kernel(const GemmParams 
       c2 = take();
     }
     // ---- epilogue (wave-private 4 KiB scratch outside the pipeline; the request stream of the next unit is already running)
-    if constexpr (SPLIT) {
-      const int g = lane >> 4, c = lane & 15;           // lane owns rows 4g + r of one column -> 64-byte row segments per atomic
+    char* wl = smem + 2 * PH_BUF + wave * 4096;
+    float cs[4][4];
+    const int nb = n0 + wc * 64;
+    float4 bias4[4];                                   // once per tile: later loads would queue behind the tile's stores
+    const bool has_bias = (EPI == 1 || EPI == 3 || EPI == 6) && p.bias != nullptr && nb < p.N;
 #pragma unroll
-      for (int i = 0; i < 8; ++i)
+    for (int j = 0; j < 4; ++j)
+      bias4[j] = has_bias ? *reinterpret_cast<const float4*>(p.bias + nb + j * 16 + 4 * (lane >> 4)) : make_float4(0.f, 0.f, 0.f, 0.f);
+    uint4 auxv[(EPI == 5) ? 16 : 1];                   // kind 5: the tile's whole aux_in block of this wave (128 rows x 64 columns)
+    if constexpr (EPI == 5) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = n0 + wc * 64 + j * 16 + c;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int m = m0 + wr * 128 + i * 16 + 4 * g + r;
-            if (m < p.M && n < p.N) atomicAdd(p.out_f32 + (int64_t)m * p.ldo_f32 + n, p.alpha * acc[i][j][r]);
-          }
-        }
-    } else {
-      char* wl = smem + 2 * PH_BUF + wave * 4096;
-      float cs[4][4];
-      const int nb = n0 + wc * 64;
-      float4 bias4[4];                                   // once per tile: later loads would queue behind the tile's stores
-      const bool has_bias = (EPI == 1 || EPI == 3 || EPI == 6) && p.bias != nullptr && nb < p.N;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        bias4[j] = has_bias ? *reinterpret_cast<const float4*>(p.bias + nb + j * 16 + 4 * (lane >> 4)) : make_float4(0.f, 0.f, 0.f, 0.f);
-      uint4 auxv[(EPI == 5) ? 16 : 1];                   // kind 5: the tile's whole aux_in block of this wave (128 rows x 64 columns)
-      if constexpr (EPI == 5) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int m = m0 + wr * 128 + q * 8 + (lane >> 3);
-          auxv[q] = (m < p.M && nb < p.N) ? *reinterpret_cast<const uint4*>(p.aux_in + (int64_t)m * p.ldaux + nb + (lane & 7) * 8) : make_uint4(0u, 0u, 0u, 0u);
-        }
+      for (int q = 0; q < 16; ++q) {
+        const int m = m0 + wr * 128 + q * 8 + (lane >> 3);
+        auxv[q] = (m < p.M && nb < p.N) ? *reinterpret_cast<const uint4*>(p.aux_in + (int64_t)m * p.ldaux + nb + (lane & 7) * 8) : make_uint4(0u, 0u, 0u, 0u);
       }
+    }
 #pragma unroll
-      for (int h = 0; h < 4; ++h) {
-        f32x4(&blk)[2][4] = reinterpret_cast<f32x4(&)[2][4]>(acc[2 * h]);
-        const int mb = m0 + wr * 128 + h * 32;
-        const uint4* pre = (EPI == 5) ? &auxv[4 * h] : nullptr;
-        if (h & 1) wave_epilogue_compact<true, EPI, 2, 2>(p, blk, mb, nb, wl, lane, cs, bias4, pre);
-        else wave_epilogue_compact<true, EPI, 2, 1>(p, blk, mb, nb, wl, lane, cs, bias4, pre);
-      }
+    for (int h = 0; h < 4; ++h) {
+      f32x4(&blk)[2][4] = reinterpret_cast<f32x4(&)[2][4]>(acc[2 * h]);
+      const int mb = m0 + wr * 128 + h * 32;
+      const uint4* pre = (EPI == 5) ? &auxv[4 * h] : nullptr;
+      if (h & 1) wave_epilogue_compact<true, EPI, 2, 2>(p, blk, mb, nb, wl, lane, cs, bias4, pre);
+      else wave_epilogue_compact<true, EPI, 2, 1>(p, blk, mb, nb, wl, lane, cs, bias4, pre);
     }
     PH_T(6)
     after_full = m0 + 256 <= p.M && n0 + 256 <= p.N;
@@ -331,43 +312,31 @@ __global__ __launch_bounds__(512, 2) void gemm256_phase_kernel(const GemmParams 
 #undef SA_QUAD
 }
 
-template <bool A_KM, bool B_KM, bool SPLIT, int EPI>
+template <bool A_KM, bool B_KM, int EPI>
 int launch256_phase_one(const GemmParams& p, hipStream_t stream, int slots) {
   static bool cfg = false;
   if (!cfg) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256_phase_kernel<A_KM, B_KM, SPLIT, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256_phase_kernel<A_KM, B_KM, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             PH_LDS) != hipSuccess) {
       sa_set_error("sa_gemm_bf16: 160 KiB of LDS per workgroup refused");
       return 2;
     }
     cfg = true;
   }
-  const int nunits = p.tiles_m * p.tiles_n * p.split_k;
+  const int nunits = p.tiles_m * p.tiles_n;
   const dim3 grid(nunits < budget_slots(slots) ? nunits : budget_slots(slots));
   GemmParams q = p;
-  const int ksteps_all = (p.K + BK - 1) / BK;
-  // the shortest K slice: slices are chunk = ceil(ksteps / split) K-tiles long, the LAST one holds what is left (the floor
-  // overstated it, e.g. 100 K-tiles in 13 slices: floor 7, last slice 4 -- the cursor then reads the next ticket before it is drawn)
-  const int chunk_nk = (ksteps_all + p.split_k - 1) / p.split_k;
-  const int min_nk = SPLIT ? ksteps_all - (p.split_k - 1) * chunk_nk : ksteps_all;
-  q.tile_counter = (min_nk >= 6 && nunits > (int)grid.x) ? sagemm::next_tile_counter(stream) : nullptr;
-  hipLaunchKernelGGL((gemm256_phase_kernel<A_KM, B_KM, SPLIT, EPI>), grid, dim3(512), PH_LDS, stream, q);
+  q.tile_counter = ((p.K + BK - 1) / BK >= 6 && nunits > (int)grid.x) ? sagemm::next_tile_counter(stream) : nullptr;
+  hipLaunchKernelGGL((gemm256_phase_kernel<A_KM, B_KM, EPI>), grid, dim3(512), PH_LDS, stream, q);
   SA_LAUNCH_CHECK("sa_gemm_bf16(256 phased)");
   return 0;
 }
 
-// returns -1 when this problem is not one the phased kernel covers (the caller then takes the general 256^2 kernels)
-template <bool A_KM, bool B_KM, bool SPLIT>
+template <bool B_KM>
 int launch256_phase(GemmParams p, hipStream_t stream) {
   p.tiles_m = (p.M + 255) / 256;
   p.tiles_n = (p.N + 255) / 256;
-  const int ksteps_all = (p.K + BK - 1) / BK;
-  if (SPLIT) {                                          // no empty K slices: both cursors walk the same unit list
-    const int chunk = (ksteps_all + p.split_k - 1) / p.split_k;
-    p.split_k = (ksteps_all + chunk - 1) / chunk;
-  } else {
-    p.split_k = 1;
-  }
+  p.split_k = 1;
   static int slots = 0;
   if (slots == 0) {
     int dev = 0;
@@ -378,28 +347,19 @@ int launch256_phase(GemmParams p, hipStream_t stream) {
     }
     slots = prop.multiProcessorCount;
   }
-  if constexpr (SPLIT) {
-    return launch256_phase_one<A_KM, B_KM, true, 0>(p, stream, slots);
-  } else {
-    switch (p.epi_kind) {
-      case 1: return launch256_phase_one<A_KM, B_KM, false, 1>(p, stream, slots);
-      case 3: return launch256_phase_one<A_KM, B_KM, false, 3>(p, stream, slots);
-      case 5: return launch256_phase_one<A_KM, B_KM, false, 5>(p, stream, slots);
-      case 6: return launch256_phase_one<A_KM, B_KM, false, 6>(p, stream, slots);
-      default: return -1;
-    }
+  switch (p.epi_kind) {
+    case 1: return launch256_phase_one<true, B_KM, 1>(p, stream, slots);
+    case 3: return launch256_phase_one<true, B_KM, 3>(p, stream, slots);
+    case 5: return launch256_phase_one<true, B_KM, 5>(p, stream, slots);
+    case 6: return launch256_phase_one<true, B_KM, 6>(p, stream, slots);
+    default:
+      sa_set_error("sa_gemm_bf16: the phased kernel has no epilogue kind %d", p.epi_kind);
+      return 1;
   }
 }
 
-
 }  // namespace
 
-int sagemm::launch_phase(GemmParams p, bool a_kmajor, bool b_kmajor, bool split, hipStream_t stream) {
-  if (split) {
-    if (!a_kmajor && !b_kmajor) return launch256_phase<false, false, true>(p, stream);
-    return -1;
-  }
-  if (a_kmajor && b_kmajor) return launch256_phase<true, true, false>(p, stream);
-  if (a_kmajor && !b_kmajor) return launch256_phase<true, false, false>(p, stream);
-  return -1;
+int sagemm::launch_phase(GemmParams p, bool b_kmajor, hipStream_t stream) {
+  return b_kmajor ? launch256_phase<true>(p, stream) : launch256_phase<false>(p, stream);
 }

@@ -286,7 +286,7 @@ def _wgrad(dY16, X16, out, rs=None):
     if wide_wgrad(N, K, rows):
         split = ops.pick_split_k(N, K, rows, tile=256)
         if split > 1:
-            if not (ops.STREAM256 and K % 4 == 0):       # (the two-stage kernel has no row sums)
+            if K % 4 != 0:                               # (bias gradient unfused: the dispatch's workspace form needs N % 4 == 0)
                 kw = {}
             ops.gemm(dY16, X16, a_kmajor=False, b_kmajor=False, out_f32=out, split_k=split, tile256=True, **kw)
             if rs is not None and not kw:
@@ -326,7 +326,7 @@ class WgradGroup:
         tile = 0
         if WGRAD_GROUP and stream_wgrad(N, K, rows):
             tile = 192
-        elif WGRAD_GROUP256 and wide_wgrad(N, K, rows) and K % 4 == 0 and ops.STREAM256:
+        elif WGRAD_GROUP256 and wide_wgrad(N, K, rows) and K % 4 == 0:
             tile = 256
         if tile and len(self.jobs) < 8 and (not self.jobs or (self.jobs[0][0].shape[0] == rows and self.tile == tile)):
             self.jobs.append((dY16, X16, out, rs))

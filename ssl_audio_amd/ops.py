@@ -117,28 +117,25 @@ def gemm(A, B, *, a_kmajor=True, b_kmajor=True, alpha=1.0, bias=None, act=0, aux
     check(lib().sa_gemm_bf16(C.byref(a), _stream()), "sa_gemm_bf16")
     e1.record()
     kind = ("NT" if b_kmajor else "NN") if a_kmajor else ("TT" if b_kmajor else "TN")
-    epi3 = (residual is not None and not res_mod and not row_group and out_f32 is not None and out_bf16 is None and act == 0 and aux_in is None
-            and aux_out is None and colsum_out is None and not accumulate and N % 64 == 0)
-    epi1 = (out_bf16 is not None and out_f32 is None and residual is None and act == 0 and aux_in is None and aux_out is None and colsum_out is None
-            and not accumulate and not row_group and N % 64 == 0)
-    kname = gemm_kernel_family(M, N, K, a_kmajor, b_kmajor, split_k, tile256, epi3, epi1)
-    nbytes = 2.0 * (M * K + N * K) + (4.0 * M * N if out_f32 is not None else 0.0) + (2.0 * M * N if out_bf16 is not None else 0.0) \
-        + (2.0 * M * N if (aux_in is not None or aux_out is not None) else 0.0) + (4.0 * M * N if residual is not None and not res_mod else 0.0)
     # the epilogue specialisation the launch compiles to (mirror of p.epi_kind in gemm_bf16.hip): with it the label is ONE rocprofv3 symbol
     # (template instance), not a kernel family -- bench.py reports both groupings
-    bf16_only = out_bf16 is not None and out_f32 is None and residual is None
-    plain = split_k == 1 and not row_group and not res_mod and not accumulate and N % 64 == 0
     epi = 0
-    if plain and bf16_only and act == 0 and aux_in is None and aux_out is None and colsum_out is None:
-        epi = 1
-    elif plain and bf16_only and act == 3 and aux_out is not None and colsum_out is None:
-        epi = 6
-    elif plain and bf16_only and act == 1 and aux_out is None and aux_in is None and colsum_out is None:
-        epi = 8
-    elif plain and epi3:
-        epi = 3
-    elif plain and bf16_only and act in (2, 4) and aux_in is not None and bias is None:
-        epi = 4 if act == 2 else 5
+    if split_k == 1 and not row_group and not res_mod and not accumulate and N % 64 == 0:
+        no_aux = aux_in is None and aux_out is None
+        if out_bf16 is not None and out_f32 is None and residual is None:
+            if act == 0 and no_aux and colsum_out is None:
+                epi = 1
+            elif act == 3 and aux_out is not None and colsum_out is None:
+                epi = 6
+            elif act == 1 and no_aux and colsum_out is None:
+                epi = 8
+            elif act in (2, 4) and aux_in is not None and bias is None:          # (the fused column sums ride along)
+                epi = 4 if act == 2 else 5
+        elif out_f32 is not None and out_bf16 is None and residual is not None and act == 0 and no_aux and colsum_out is None:
+            epi = 3
+    kname = gemm_kernel_family(M, N, K, a_kmajor, b_kmajor, split_k, tile256, epi3=epi == 3, epi1=epi == 1)
+    nbytes = 2.0 * (M * K + N * K) + (4.0 * M * N if out_f32 is not None else 0.0) + (2.0 * M * N if out_bf16 is not None else 0.0) \
+        + (2.0 * M * N if (aux_in is not None or aux_out is not None) else 0.0) + (4.0 * M * N if residual is not None and not res_mod else 0.0)
     GEMM_PROFILE.append((e0, e1, 2.0 * M * N * K, kind + ("/splitk" if split_k > 1 else ""), nbytes, kname, f"{kname}<{kind}, epilogue {epi}>"))
 
 
@@ -224,11 +221,8 @@ def gemm_wgrad_group(dY, X, out, split_k, tile=192, asum_out=None, asum_index=-1
     GEMM_PROFILE.append((e0, e1, flops, "TN/splitk", nbytes, kname, f"{kname}<group of {n}>"))
 
 
-STREAM256 = os.environ.get("SA_GEMM_WGRAD_STREAM256", "1") != "0"      # (mirror of gemm_dispatch's default for TN split-K on the 256 tile)
-
-
 def gemm_kernel_family(M, N, K, a_kmajor, b_kmajor, split_k, tile256, epi3=False, epi1=False):
-    """Which device kernel sa_gemm_bf16 dispatches to by default (mirror of the selection in gemm_bf16.hip, no SA_GEMM_TILE
+    """Which device kernel sa_gemm_bf16 dispatches to by default (mirror of select_kernel in gemm_bf16.hip, no SA_GEMM_TILE
     override); used to label bench.py's per-launch timings with the names rocprofv3 reports.  epi3: the launch has the compact
     bias + residual -> fp32 epilogue (proj / fc2 forward), which the forward layout runs on the phased kernel; epi1: the compact
     (bias ->) bf16 epilogue, phased too once the reduction is long (K >= 1536: the fc1 / qkv data gradients)."""
@@ -236,7 +230,7 @@ def gemm_kernel_family(M, N, K, a_kmajor, b_kmajor, split_k, tile256, epi3=False
         if int(tile256) == 2:
             return "gemm_tn_stream_kernel"
         if tile256:
-            return "gemm_tn_stream256_kernel" if (not a_kmajor and not b_kmajor and STREAM256) else "gemm256_kernel<split-K>"
+            return "gemm_tn_stream256_kernel"
         return "gemm_kernel<split-K>"
     big = M >= 1024 and N >= 192 and ((M + 255) // 256) * ((N + 255) // 256) >= 128
     if not big:

@@ -1,5 +1,5 @@
-"""Helper for test_kernels_gpu.py::test_gemm_tile_modes: run in a subprocess with SA_GEMM_TILE / SA_GEMM_WGRAD_RING set
-(the library reads them once), checks every operand layout of a large ragged problem against an fp64 CPU product."""
+"""Helper for test_kernels_gpu.py::test_gemm_tile_modes: run in a subprocess with SA_GEMM_TILE set (the library reads it once),
+checks every operand layout of a large ragged problem against an fp64 CPU product."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -133,9 +133,9 @@ def main():
     assert float((runs[True][4].cpu().double() - r5).norm() / r5.norm()) < 4e-3
     assert float((runs[True][5].cpu().double() - r5.sum(0)).norm() / r5.sum(0).norm()) < 1e-4
     # split-K weight gradient under dynamic hand-out with a RAGGED last K slice: 100 K-tiles in 13 slices of 8 leave a last
-    # slice of 4, shorter than the phased kernel's ticket look-ahead, so that kernel must fall back to static striding for this launch;
-    # 4 x 5 tiles x 13 slices = 260 units > 256 workgroups.  Atomic accumulation (no workspace) is the form SA_GEMM_WGRAD_PHASE=1 /
-    # SA_GEMM_WGRAD_RING=1 take; dynamic and static must agree to fp32 summation-order noise and be right against fp64.
+    # slice of 4, shorter than the ticket look-ahead of the split-K phased kernel this case was written for (since removed);
+    # 4 x 5 tiles x 13 slices = 260 units > 256 workgroups.  With atomic accumulation (no workspace) dynamic and static must agree to
+    # fp32 summation-order noise and be right against fp64.
     Ts, Ns, Ks = 6400, 1024, 1280
     dYs = bf(torch.randn(Ts, Ns, generator=g)).to(dev); Xs = bf(torch.randn(Ts, Ks, generator=g)).to(dev)
     refs = dYs.cpu().double().T @ Xs.cpu().double()
@@ -156,7 +156,7 @@ def main():
             assert float((outs[0] - outs[1]).abs().max()) <= 1e-4 * float(outs[0].abs().max())
     ops.DETERMINISTIC_WGRAD = det
     torch.cuda.synchronize()
-    print(f"ok tile={os.environ.get('SA_GEMM_TILE', 'default')} ring_wgrad={os.environ.get('SA_GEMM_WGRAD_RING', '0')} worst={worst:.2e} wgrad={ew:.2e}")
+    print(f"ok tile={os.environ.get('SA_GEMM_TILE', 'default')} worst={worst:.2e} wgrad={ew:.2e}")
 
 
 if __name__ == "__main__":
