@@ -225,6 +225,19 @@ int sa_ema_update_gated(float* target, const float* online, int64_t n, float bet
  * scratch2: 2 floats (squared norms), required with lars_adaptation; p_bf16 (optional): refreshed bf16 copy. */
 int sa_lars_step(float* p, const float* g, float* mu, int64_t n, float lr, float weight_decay, float momentum, float eta,
                  int32_t lars_adaptation, float* scratch2, void* p_bf16, void* stream);
+/* LARS over every tensor of a flat parameter buffer in two launches (utils/utils.py:150-189, the optimiser main.py:326-345 builds with
+ * weight_decay_filter = lars_adaptation_filter = True).  segments: n_segments device rows of four int64 {start, count, chunk_base, flags},
+ * one per tensor, ascending chunk_base: the tensor is p[start, start + count) (start a multiple of 8), cut into SA_LARS_CHUNK-element
+ * chunks numbered chunk_base, chunk_base + 1, ...; n_chunks = total chunk count; flags = group row (bits 0-7: the tensor's lr is
+ * hyper[row * hyper_stride], row < hyper_rows) | 256 (decay: dp = g + weight_decay * p, else dp = g) | 512 (adapt: dp *= eta |p| / |dp|,
+ * 1 when either norm is 0).  Then mu = momentum * mu + dp; p -= lr * mu; p_bf16 (optional) receives bf16(p).  Elements in no segment
+ * are not touched.  partials: 2 * n_chunks floats of scratch (one fixed slot per chunk: no atomics, bitwise reproducible).  skip_flag
+ * (optional): *skip_flag != 0 leaves p, mu and p_bf16 untouched.  With no segment adapted or decayed and momentum 0 this is SGD
+ * (p -= lr * g; main.py:323-325).  p, g, mu, p_bf16 16-byte aligned. */
+#define SA_LARS_CHUNK 8192
+int sa_lars_flat_step(float* p, const float* g, float* mu, void* p_bf16, int64_t n, const int64_t* segments, int32_t n_segments,
+                      int64_t n_chunks, const float* hyper, int32_t hyper_rows, int32_t hyper_stride, float weight_decay, float momentum,
+                      float eta, float* partials, const int32_t* skip_flag, void* stream);
 /* y += a * x on flat fp32 buffers (gradient accumulation of small vectors) */
 int sa_axpy_f32(float* y, const float* x, int64_t n, float a, void* stream);
 /* flag[0] += number of non-finite values in x[0..n): the device-side half of the reference's per-step `math.isfinite(loss.item())`

@@ -61,6 +61,8 @@ SCHEMAS = {
                    "float grad_scale=1.0, Tensor(d!)? p_bf16=None) -> ()"),
     "lars_step": ("sa_lars_step", "(Tensor(a!) p, Tensor g, Tensor(b!) mu, float lr, float wd, float momentum, float eta, bool adapt, "
                   "Tensor(c!)? scratch2=None, Tensor(d!)? p_bf16=None) -> ()"),
+    "lars_flat_step": ("sa_lars_flat_step", "(Tensor(a!) p, Tensor g, Tensor(b!) mu, Tensor segments, int n_chunks, Tensor hyper, float wd, float momentum, "
+                       "float eta, Tensor(c!) partials, Tensor(d!)? p_bf16=None, Tensor? skip_flag=None) -> ()"),
     "adamw_step_dev": ("sa_adamw_step_dev", "(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor hyper3, float beta1, float beta2, float eps, float wd, "
                        "float grad_scale=1.0, Tensor(d!)? p_bf16=None, Tensor? skip_flag=None) -> ()"),
     "ema_update": ("sa_ema_update", "(Tensor(a!) target, Tensor online, float beta) -> ()"),

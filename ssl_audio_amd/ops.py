@@ -486,6 +486,45 @@ def lars_step(p, g, mu, lr, wd, momentum, eta, adapt, scratch2=None, p_bf16=None
                              float(eta), int(bool(adapt)), _p(scratch2), _p(p_bf16), _stream()), "sa_lars_step")
 
 
+LARS_CHUNK = 8192                 # SA_LARS_CHUNK (include/ssl_audio_hip.h): elements per partial-sum slot of sa_lars_flat_step
+LARS_DECAY, LARS_ADAPT = 256, 512  # segment flags above the group row
+
+
+def lars_segment_table(segments, device):
+    """sa_lars_flat_step's segment table from host tuples (start, count, row, decay, adapt), one per tensor in ascending `start`.
+    Returns (table: int64 [n, 4] on `device`, n_chunks); the partials workspace is 2 * n_chunks floats."""
+    rows, base = [], 0
+    for start, count, row, decay, adapt in segments:
+        if start % 8 or count <= 0 or not 0 <= row < 256:
+            raise ValueError(f"lars_segment_table: segment (start {start}, count {count}, row {row}) needs start % 8 == 0, count > 0, 0 <= row < 256")
+        if rows and start < rows[-1][0] + rows[-1][1]:
+            raise ValueError(f"lars_segment_table: segment at {start} overlaps or precedes the one before it")
+        rows.append([start, count, base, row | (LARS_DECAY if decay else 0) | (LARS_ADAPT if adapt else 0)])
+        base += (count + LARS_CHUNK - 1) // LARS_CHUNK
+    table = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4)
+    return table.to(device), base
+
+
+def lars_flat_step(p, g, mu, segments, n_chunks, hyper, wd, momentum, eta, partials, p_bf16=None, skip_flag=None):
+    """LARS over every segment of flat fp32 buffers in two launches (sa_lars_flat_step): segments / n_chunks from lars_segment_table,
+    hyper [rows, stride] device fp32 (lr of group r at hyper[r, 0]), partials >= 2 * n_chunks fp32 scratch.  The buffers cover
+    [0, g.numel()); p, mu (and p_bf16) may be longer."""
+    n = g.numel()
+    if p.numel() < n or mu.numel() < n or (p_bf16 is not None and p_bf16.numel() < n):
+        raise ValueError(f"lars_flat_step: p / mu / p_bf16 must hold at least the {n} elements of g")
+    if segments.dtype != torch.int64 or segments.dim() != 2 or segments.shape[1] != 4 or not segments.is_contiguous() or not segments.is_cuda:
+        raise ValueError("lars_flat_step: segments must be a contiguous int64 [n, 4] device tensor (lars_segment_table)")
+    if hyper.dim() != 2 or hyper.stride(1) != 1 or partials.numel() < 2 * n_chunks:
+        raise ValueError("lars_flat_step: hyper must be 2-D with unit inner stride and partials hold 2 * n_chunks floats")
+    if p_bf16 is not None and p_bf16.dtype != BF16:
+        raise TypeError(f"lars_flat_step: p_bf16 must be bfloat16, got {p_bf16.dtype}")
+    # algorithmic bytes per parameter: pass 1 reads p, g (8 B); pass 2 reads p, g, mu (12 B), writes p, mu (8 B) and the bf16 copy (2 B)
+    _timed("lars_flat_update_kernel", float(n) * (28 + (2 if p_bf16 is not None else 0)), lambda: check(
+        lib().sa_lars_flat_step(_p(_req(p, F32, "p")), _p(_req(g, F32, "g")), _p(_req(mu, F32, "mu")), _p(p_bf16), n, _p(segments),
+                                segments.shape[0], int(n_chunks), _p(_req(hyper, F32, "hyper")), hyper.shape[0], hyper.stride(0), float(wd),
+                                float(momentum), float(eta), _p(_req(partials, F32, "partials")), _p(skip_flag), _stream()), "sa_lars_flat_step"))
+
+
 def ema_update(target, online, beta):
     check(lib().sa_ema_update(_p(target), _p(online), target.numel(), float(beta), _stream()), "sa_ema_update")
 

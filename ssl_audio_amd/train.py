@@ -36,6 +36,8 @@ class FlatState:
     """
 
     def __init__(self, named_params, device):
+        named_params = list(named_params)
+        self.named = named_params                         # module parameter order (get_optimizer's LARS groups follow it)
         decay, nodecay, frozen = [], [], []
         for name, p in named_params:
             if not p.requires_grad:
@@ -94,6 +96,8 @@ class FlatState:
         # memory by one small async copy per step.
         self.hyper = torch.zeros(2, 4, device=device)
         self.sync = None           # the GradSync that reduces self.grads over ranks (engine.block_done_hook finds it through the sinks)
+        self._tables = {}          # segment tables of the flat LARS / SGD launch (built once; see flat_table)
+        self._partials = None
 
     def bind_bf16(self):
         """Point the engine's bf16 weight cache at views of the flat bf16 buffer (kept fresh by the AdamW kernel)."""
@@ -147,6 +151,65 @@ class FlatState:
                            self.step_count, grad_scale, self.params_bf16[nd:nt])
         self.epoch[0] += 1                    # copies derived from the bf16 weights (transposed dgrad operands) are stale now
         engine.BF16_WEIGHTS_T.refresh_all(self._param_ids)   # ... and rebuilt here, all of this state's in one launch
+
+    # ------------------------------------------------------------------ LARS / SGD (utils/utils.py:150-189, main.py:318-345)
+    def flat_table(self, kind="lars", weight_decay_filter=True, lars_adaptation_filter=True):
+        """(segment table, chunk count) of sa_lars_flat_step over this state's trained parameters, built on first use.  One segment per
+        parameter; its group row is get_optimizer's LARS group (main.py:326-345: 0 = ndim != 1 weights, 1 = ndim == 1 biases), which must be
+        this state's decayed / un-decayed split -- the two rows of self.hyper.  kind 'lars': decay / adaptation as the filters say (both skip
+        1-D tensors); kind 'sgd': neither, for all segments.  The zero pads between parameters are in no segment."""
+        key = (kind, bool(weight_decay_filter), bool(lars_adaptation_filter)) if kind == "lars" else (kind,)
+        if key not in self._tables:
+            if kind not in ("lars", "sgd"):
+                raise ValueError(f"flat_table: kind must be 'lars' or 'sgd', got {kind!r}")
+            segs = []
+            for n, p in self._trainable():
+                off, cnt = self.offsets[n]
+                decayed = off < self.n_decay
+                if kind == "lars" and decayed != (p.dim() != 1):
+                    raise ValueError(f"LARS: parameter {n} (shape {tuple(p.shape)}) is {'' if decayed else 'not '}weight-decayed here but in the "
+                                     f"{'bias' if p.dim() == 1 else 'weight'} group of get_optimizer (main.py:326-345); the flat state needs the two to coincide")
+                one_d = p.dim() == 1
+                if kind == "lars":
+                    segs.append((off, cnt, 0 if decayed else 1, not (weight_decay_filter and one_d), not (lars_adaptation_filter and one_d)))
+                else:
+                    segs.append((off, cnt, 0 if decayed else 1, False, False))
+            segs.sort()
+            self._tables[key] = ops.lars_segment_table(segs, self.params.device)
+            need = max(2 * self._tables[key][1], 1)
+            if self._partials is None or self._partials.numel() < need:
+                self._partials = torch.empty(need, device=self.params.device)
+        return self._tables[key]
+
+    def lars_staged(self, wd, momentum=0.9, eta=0.001, weight_decay_filter=True, lars_adaptation_filter=True, skip_flag=None):
+        """One LARS step over every trained parameter (sa_lars_flat_step: two launches), the counterpart of adamw_staged: the learning rate
+        of each group is read from self.hyper (row 0 weights, row 1 biases; stage_hyper(lr_weights, lr_nodecay=lr_biases)), the momentum
+        buffer is self.m, the bf16 weights are refreshed in the same pass.  skip_flag: device word, non-zero = change nothing."""
+        table, n_chunks = self.flat_table("lars", weight_decay_filter, lars_adaptation_filter)
+        ops.lars_flat_step(self.params, self.grads, self.m, table, n_chunks, self.hyper, wd, momentum, eta, self._partials, self.params_bf16,
+                           skip_flag)
+        self.epoch[0] += 1
+        engine.BF16_WEIGHTS_T.refresh_all(self._param_ids)
+
+    def sgd_staged(self, skip_flag=None):
+        """torch.optim.SGD(lr, momentum = 0, weight_decay = 0) -- main.py:323-325 forces wd = 0 -- as the flat LARS launch with no decay, no
+        adaptation and no momentum: p -= lr * g, lr per get_param_groups group from self.hyper."""
+        table, n_chunks = self.flat_table("sgd")
+        ops.lars_flat_step(self.params, self.grads, self.m, table, n_chunks, self.hyper, 0.0, 0.0, 0.0, self._partials, self.params_bf16, skip_flag)
+        self.epoch[0] += 1
+        engine.BF16_WEIGHTS_T.refresh_all(self._param_ids)
+
+    def lars_groups(self):
+        """get_optimizer's two LARS groups over this state's module (main.py:326-345): ([(name, p)] with ndim != 1, [(name, p)] with
+        ndim == 1), each in module parameter order, frozen parameters included (model.parameters() holds them; they never get state)."""
+        return [(n, p) for n, p in self.named if p.dim() != 1], [(n, p) for n, p in self.named if p.dim() == 1]
+
+    def optim_state_dict_lars(self, lr_weights, lr_biases, wd, momentum=0.9, eta=0.001):
+        """This state's momentum in `utils.LARS(...).state_dict()` form (see lars_state_dict)."""
+        return lars_state_dict([self], lr_weights, lr_biases, wd, momentum, eta)
+
+    def load_optim_state_dict_lars(self, sd):
+        load_lars_state_dict([self], sd)
 
     # ------------------------------------------------------------------ checkpoint / resume (main_bt_byol.py:492-503, utils/utils.py:37-46)
     def _trainable(self):
@@ -211,6 +274,57 @@ class FlatState:
             ops.ema_update(self.params, other.params, beta)
         ops.cast_bf16(self.params, self.params_bf16)
         self.epoch[0] += 1
+
+
+def _lars_entries(flats):
+    """(flat state, name, parameter) in get_optimizer's LARS index order over several flat states (encoder, then predictor): every
+    state's weights, then every state's biases (main_bt_byol.py:317-341 fills the two groups module by module)."""
+    groups = [fl.lars_groups() for fl in flats]
+    w = [(fl, n, p) for fl, (gw, _) in zip(flats, groups) for n, p in gw]
+    b = [(fl, n, p) for fl, (_, gb) in zip(flats, groups) for n, p in gb]
+    return w, b
+
+
+def lars_state_dict(flats, lr_weights, lr_biases, wd, momentum=0.9, eta=0.001):
+    """The momentum buffers of flat states in the form `utils.LARS(parameters, lr=0, weight_decay=wd, weight_decay_filter=True,
+    lars_adaptation_filter=True).state_dict()` has for get_optimizer's two groups (main.py:326-345): state[i] = {'mu': ...} for every
+    trained parameter, i counted over the weights group, then the biases group."""
+    w, b = _lars_entries(flats)
+    state = {}
+    for i, (fl, n, p) in enumerate(w + b):
+        if p.requires_grad:
+            off, cnt = fl.offsets[n]
+            state[i] = {"mu": fl.m[off:off + cnt].view(p.shape).clone()}
+    group = lambda lr, idx: dict(lr=lr, weight_decay=wd, momentum=momentum, eta=eta, weight_decay_filter=True, lars_adaptation_filter=True,
+                                 params=idx)
+    return {"state": state, "param_groups": [group(lr_weights, list(range(len(w)))), group(lr_biases, list(range(len(w), len(w) + len(b))))]}
+
+
+def load_lars_state_dict(flats, sd):
+    """Inverse of lars_state_dict; also reads `ssl_audio_amd.utils.LARS`'s own state dicts (their extra 'scratch' entries are ignored).
+    A parameter without a state entry (never stepped) starts from a zero momentum."""
+    w, b = _lars_entries(flats)
+    groups = sd["param_groups"]
+    if len(groups) != 2 or len(groups[0]["params"]) != len(w) or len(groups[1]["params"]) != len(b):
+        raise ValueError(f"LARS state with groups of {[len(g['params']) for g in groups]} parameters; get_optimizer's LARS groups here hold "
+                         f"[{len(w)}, {len(b)}]")
+    for fl in flats:
+        fl.m.zero_()
+    for idx, (fl, n, p) in zip(groups[0]["params"] + groups[1]["params"], w + b):
+        st = sd["state"].get(idx)
+        if st is None or not p.requires_grad:
+            continue
+        if tuple(st["mu"].shape) != tuple(p.shape):
+            raise ValueError(f"LARS state {idx} has shape {tuple(st['mu'].shape)}, parameter {n} has {tuple(p.shape)}")
+        off, cnt = fl.offsets[n]
+        fl.m[off:off + cnt].copy_(st["mu"].reshape(-1).to(fl.m.device, torch.float32))
+
+
+def _as_sgd_state_dict(sd):
+    """torch.optim.SGD(groups, lr, weight_decay=0).state_dict() over the groups of an AdamW-form dictionary: momentum 0 keeps no state."""
+    keys = lambda g: dict(lr=g["lr"], momentum=0, dampening=0, weight_decay=0, nesterov=False, maximize=False, foreach=None, differentiable=False,
+                          fused=None, params=g["params"])
+    return {"state": {}, "param_groups": [keys(g) for g in sd["param_groups"]]}
 
 
 def merge_optim_state_dicts(*sds):
@@ -349,17 +463,39 @@ class BarlowTwinsTrainer:
     configs 2-3).  mode='byol': online (+predictor) / EMA target, two cross terms (main_bt_byol.py --stop_gradient
     --predictor, BASELINE config 4).  mode='mae': main.py:69-125 with `--mask --mask_ratio r --masked_recon` (BASELINE config 5):
     view 1 goes through the masked encoder + MAE decoder (teacher side, adds the reconstruction loss), view 2 through the
-    unmasked encoder, one BT term between them."""
+    unmasked encoder, one BT term between them.
+
+    The optimiser is cfg.optimizer, as get_optimizer builds it (main.py:314-345): 'AdamW' (lr, wd), 'Adam' (AdamW with wd = 0), 'SGD'
+    (lr, wd = 0, no momentum) and 'LARS' (lr_weights / lr_biases, wd, both filters on), each as flat launches over FlatState.  The
+    convolutional encoders (resnet18, resnet18_ReGP_NRF, audiontt: BatchNorm with batch statistics) run mode 'bt' without local crops,
+    with the two views as two encoder passes (main.py:86-109)."""
+
+    OPTIMIZERS = ("AdamW", "Adam", "SGD", "LARS")
+    CONV_ENCODERS = ("resnet18", "resnet18_ReGP_NRF", "audiontt")
 
     def __init__(self, cfg, device, mode="bt", batch_per_rank=None, clip_samples=160000, seed=0, from_waveform=True,
                  ema_beta=0.99, grad_dtype=None):
         self.cfg, self.device, self.mode = cfg, device, mode
+        self.optimizer = getattr(cfg, "optimizer", None) or "AdamW"
+        if self.optimizer not in self.OPTIMIZERS:
+            raise ValueError(f"optimizer {self.optimizer!r}: expected one of {self.OPTIMIZERS} (main.py:318-345)")
+        lr_keys = ("lr_weights", "lr_biases") if self.optimizer == "LARS" else ("lr",)
+        missing = [k for k in lr_keys if getattr(cfg, k, None) is None]
+        if missing:
+            raise ValueError(f"optimizer {self.optimizer} needs cfg.{' and cfg.'.join(missing)} (utils/hyperparameters.py:101-110 sets them per model)")
+        # the convolutional encoders keep BatchNorm batch statistics: two passes (view 1, view 2) as main.py:86-109, built for 'bt' only
+        self.two_pass = cfg.model_type in self.CONV_ENCODERS
+        if self.two_pass and (mode != "bt" or int(getattr(cfg, "local_crops_number", 0) or 0) or getattr(cfg, "mask", False)
+                              or getattr(cfg, "masked_recon", False)):
+            raise NotImplementedError(f"{cfg.model_type} in the trainer: mode 'bt' without local crops, masking or reconstruction only "
+                                      f"(got mode {mode!r}, local_crops_number {getattr(cfg, 'local_crops_number', 0)})")
         self.world = sdist.get_world_size()
         self.B = batch_per_rank or cfg.batch_size // self.world
         self.clip_samples = clip_samples
         self.from_waveform = from_waveform
         torch.manual_seed(seed)
-        self.online = MultiCropWrapper(ModelWrapper(cfg), BarlowTwinsHead(cfg, _feature_dim(cfg))).to(device)
+        backbone = ModelWrapper(cfg)
+        self.online = MultiCropWrapper(backbone, BarlowTwinsHead(cfg, backbone.feature_dim)).to(device)
         self.flat = FlatState(list(self.online.named_parameters()), device)
         # local crops (main.py:86-119 with ncrops = L + 2): the teacher sees global view 1, the student global view 2 and the L local views
         self.L = int(getattr(cfg, "local_crops_number", 0) or 0)
@@ -374,7 +510,8 @@ class BarlowTwinsTrainer:
             self.predictor = BarlowTwinsPredictor(cfg.projector_out_dim, use=True).to(device)
             self.flat_pred = FlatState(list(self.predictor.named_parameters()), device)
             self.sync_pred = self.flat_pred.sync = GradSync(self.flat_pred, grad_dtype=grad_dtype)
-            self.target = MultiCropWrapper(ModelWrapper(cfg), BarlowTwinsHead(cfg, _feature_dim(cfg))).to(device)
+            tb = ModelWrapper(cfg)
+            self.target = MultiCropWrapper(tb, BarlowTwinsHead(cfg, tb.feature_dim)).to(device)
             self.target.load_state_dict(self.online.state_dict())
             for p in self.target.parameters():
                 p.requires_grad = False
@@ -387,13 +524,20 @@ class BarlowTwinsTrainer:
                                           cfg.mixup_ratio, virtual_crop_scale=tuple(cfg.virtual_crop_scale), seed=seed + 1000 * sdist.get_rank(),
                                           local_crops_number=self.L, local_crops_size=tuple(cfg.local_crops_size), gnoise=bool(cfg.Gnoise))
         self.post_norm = NormalizeBatch() if cfg.post_norm else None
-        self.wd = cfg.wd
+        self.wd = 0.0 if self.optimizer in ("Adam", "SGD") else cfg.wd          # get_optimizer sets args.wd = 0 for Adam and SGD
         # What `optimizer.param_groups` is to the reference's loop: utils.adjust_learning_rate(args, trainer, loader, iteration) --
         # main.py:52's call with this object in the optimiser's place -- writes the step's learning rates here, in get_optimizer's group
-        # order (encoder decayed / un-decayed, then the predictor's two groups); the fused AdamW launches read them.
-        self.param_groups = [{"lr": cfg.lr, "weight_decay": cfg.wd}, {"lr": cfg.lr, "weight_decay": 0.0}]
-        if mode == "byol":
-            self.param_groups += [{"lr": cfg.lr, "weight_decay": cfg.wd}, {"lr": cfg.lr, "weight_decay": 0.0}]
+        # order (encoder decayed / un-decayed, then the predictor's two groups; LARS: weights, biases -- encoder and predictor together);
+        # the flat optimiser launches read them.
+        if self.optimizer == "LARS":
+            self.param_groups = [{"lr": cfg.lr_weights, "weight_decay": cfg.wd}, {"lr": cfg.lr_biases, "weight_decay": cfg.wd}]
+        else:
+            self.param_groups = [{"lr": cfg.lr, "weight_decay": self.wd}, {"lr": cfg.lr, "weight_decay": 0.0}]
+            if mode == "byol":
+                self.param_groups += [{"lr": cfg.lr, "weight_decay": self.wd}, {"lr": cfg.lr, "weight_decay": 0.0}]
+        for fl in (self.flat, self.flat_pred):             # LARS / SGD: the segment tables are built (and checked) now, not inside a capture
+            if fl is not None and self.optimizer in ("LARS", "SGD"):
+                fl.flat_table(self.optimizer.lower())
         self._graph = self._graph_views = self._graph_loss = None
         self._graph_mask_ratio = None                    # the mask ratio a captured step was recorded with (None: unmasked)
         self.use_graph = True                            # False: run eagerly although a graph exists (profiling passes with per-launch events)
@@ -494,7 +638,8 @@ class BarlowTwinsTrainer:
         g = self.param_groups
         self.flat.stage_hyper(g[0]["lr"], lr_nodecay=g[1]["lr"])
         if self.mode == "byol":
-            self.flat_pred.stage_hyper(g[2]["lr"], lr_nodecay=g[3]["lr"])
+            gp = g[2:4] if len(g) == 4 else g[:2]           # (LARS: the predictor is in the encoder's two groups)
+            self.flat_pred.stage_hyper(gp[0]["lr"], lr_nodecay=gp[1]["lr"])
         if self._graph is not None and self.use_graph:
             # the captured step holds ITS mask ratio (the token counts are baked into its launches): another ratio cannot be replayed
             if mask_ratio is not None and self._graph_mask_ratio is not None and float(mask_ratio) != float(self._graph_mask_ratio):
@@ -519,7 +664,13 @@ class BarlowTwinsTrainer:
         masked = self.mode == "mae" or bool(getattr(self.cfg, "mask", False))
         mr = (self.cfg.mask_ratio if mask_ratio is None else mask_ratio) if masked else 0
         recon_on = self.mode == "mae" or bool(getattr(self.cfg, "masked_recon", False))
-        if self.mode == "bt" and self.L == 0 and not masked and not recon_on:
+        if self.two_pass:
+            # main.py:86-109 for an encoder with BatchNorm: teacher = model(images[:1]), student = model(images[1:]), each pass with its
+            # own batch statistics and running-stat update
+            t = self.online(views[:1], ncrops=1)
+            st = self.online(views[1:2], ncrops=1)
+            loss = self.criterion(st, t, ngcrops_each=1)
+        elif self.mode == "bt" and self.L == 0 and not masked and not recon_on:
             z = self.online(views, ncrops=2)
             z1, z2 = z.chunk(2)
             loss = self.criterion.forward_loss(z1, z2)
@@ -559,11 +710,20 @@ class BarlowTwinsTrainer:
         self.sync.finish()
         # a non-finite loss (counted just above) turns the optimiser launches into no-ops: the reference exits before optimizer.step()
         # (main_bt_byol.py:116-118); here the host reads the counter lazily, so the weights and moments are kept clean on the device
-        self.flat.adamw_staged(self.wd, skip_flag=self._nonfinite)
+        self._optimizer_step(self.flat)
         if self.mode == "byol":
             self.sync_pred.finish()
-            self.flat_pred.adamw_staged(self.wd, skip_flag=self._nonfinite)
+            self._optimizer_step(self.flat_pred)
         return loss.detach()
+
+    def _optimizer_step(self, flat):
+        """cfg.optimizer's update of one flat state, gated by the non-finite-loss counter (capturable: all scalars that change are in flat.hyper)."""
+        if self.optimizer == "LARS":
+            flat.lars_staged(self.wd, skip_flag=self._nonfinite)           # utils.LARS defaults: momentum 0.9, eta 0.001; both filters on
+        elif self.optimizer == "SGD":
+            flat.sgd_staged(skip_flag=self._nonfinite)
+        else:
+            flat.adamw_staged(self.wd, skip_flag=self._nonfinite)
 
     # ------------------------------------------------------------------ HIP graph
     def enable_graph(self, views=None):
@@ -613,24 +773,34 @@ class BarlowTwinsTrainer:
 
         'optimizer' is what the reference driver's own optimiser would save: get_optimizer (main_bt_byol.py:301-305) builds ONE AdamW over
         get_param_groups(encoder) + get_param_groups(predictor) -- four groups, the last two empty without a predictor -- and
-        `driver="main"` gives main.py's two-group form.  Refuses to save after a non-finite loss (the reference stops before the optimiser
+        `driver="main"` gives main.py's two-group form (Adam and SGD alike; LARS always has its two groups, main.py:326-345).  Refuses to save after a non-finite loss (the reference stops before the optimiser
         step, main_bt_byol.py:116-118; here the flag is read lazily, so it is read now)."""
         self.assert_finite()
-        opt = self.flat.optim_state_dict(self.lr, self.wd)
-        if driver == "main_bt_byol":
-            n_enc = sum(len(g["params"]) for g in opt["param_groups"])
-            pred = self.flat_pred.optim_state_dict(self.lr, self.wd, index_base=n_enc) if self.mode == "byol" else _empty_groups(self.lr, self.wd)
-            opt = merge_optim_state_dicts(opt, pred)
-        elif self.mode == "byol":
+        if driver != "main_bt_byol" and self.mode == "byol":
             raise ValueError("driver='main' has no predictor; a byol trainer saves main_bt_byol.py's form")
-        for saved, live in zip(opt["param_groups"], self.param_groups):       # the learning rates the schedule last set
-            saved["lr"] = live["lr"]
+        if self.optimizer == "LARS":
+            # get_optimizer's LARS: two groups, the predictor's parameters in the encoder's groups (main_bt_byol.py:317-341)
+            flats = [self.flat] + ([self.flat_pred] if self.mode == "byol" else [])
+            opt = lars_state_dict(flats, self.param_groups[0]["lr"], self.param_groups[1]["lr"], self.wd)
+        else:
+            opt = self._grouped_optim_state_dict(driver)
         sd = {"model": self.online.state_dict(), "optimizer": opt, "epoch": epoch,
               "barlow_twins_loss": self.criterion.state_dict(), "steps": self._steps}
         if self.mode == "byol":
             sd["predictor"] = self.predictor.state_dict()
             sd["target"] = self.target.state_dict()
         return sd
+
+    def _grouped_optim_state_dict(self, driver):
+        """AdamW / Adam / SGD over get_param_groups' groups (two per network)."""
+        opt = self.flat.optim_state_dict(self.lr, self.wd)
+        if driver == "main_bt_byol":
+            n_enc = sum(len(g["params"]) for g in opt["param_groups"])
+            pred = self.flat_pred.optim_state_dict(self.lr, self.wd, index_base=n_enc) if self.mode == "byol" else _empty_groups(self.lr, self.wd)
+            opt = merge_optim_state_dicts(opt, pred)
+        for saved, live in zip(opt["param_groups"], self.param_groups):       # the learning rates the schedule last set
+            saved["lr"] = live["lr"]
+        return _as_sgd_state_dict(opt) if self.optimizer == "SGD" else opt
 
     def load_state_dict(self, ckpt):
         """Resume from state_dict()'s dictionary, or from a checkpoint of the reference driver (utils/utils.py:37-46: 'model', 'optimizer'
@@ -639,14 +809,19 @@ class BarlowTwinsTrainer:
         self.online.load_state_dict(strip(ckpt["model"]))
         self.flat.refresh_from_parameters()
         opt = ckpt.get("optimizer")
-        if opt is not None:
+        if opt is not None and self.optimizer == "LARS":
+            load_lars_state_dict([self.flat] + ([self.flat_pred] if self.mode == "byol" else []), opt)
+            for live, saved in zip(self.param_groups, opt["param_groups"]):
+                live["lr"] = saved["lr"]
+        elif opt is not None:
             if len(opt["param_groups"]) not in (2, 4):
                 raise ValueError(f"optimizer state with {len(opt['param_groups'])} parameter groups: expected main.py's 2 (encoder) or "
                                  "main_bt_byol.py's 4 (encoder + predictor, --stop_gradient)")
-            self.flat.load_optim_state_dict(opt, 0)
+            if self.optimizer != "SGD":                             # (SGD without momentum keeps no state)
+                self.flat.load_optim_state_dict(opt, 0)
             if len(opt["param_groups"]) == 4:
                 n_pred = len(opt["param_groups"][2]["params"]) + len(opt["param_groups"][3]["params"])
-                if self.mode == "byol":
+                if self.mode == "byol" and self.optimizer != "SGD":
                     self.flat_pred.load_optim_state_dict(opt, 2)
                 elif n_pred:
                     raise ValueError(f"the checkpoint's optimizer holds {n_pred} predictor parameters; this trainer (mode '{self.mode}') has no predictor")
@@ -697,6 +872,3 @@ class _FrozenFlat:
     ema_from = FlatState.ema_from
     refresh_from_parameters = FlatState.refresh_from_parameters
 
-
-def _feature_dim(cfg):
-    return {"tiny": 192, "small": 384, "base": 768, "large": 1024}[cfg.model_type.split("_")[-1]]

@@ -158,6 +158,7 @@ class LARS(torch.optim.Optimizer):
                 st = self.state[p]
                 if "mu" not in st:
                     st["mu"] = torch.zeros_like(p)
+                if "scratch" not in st:                  # (a state dict in the reference's form carries the momentum only)
                     st["scratch"] = torch.empty(2, dtype=torch.float32, device=p.device)
                 ops.lars_step(p, p.grad, st["mu"], group["lr"], wd, group["momentum"], group["eta"], adapt, st["scratch"])
                 BF16_WEIGHTS.mark_modified(p)
