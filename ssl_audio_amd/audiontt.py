@@ -13,9 +13,8 @@ ReLU kernel; `keep=` makes it explicit for parity tests.
 import torch
 import torch.nn as nn
 
-from . import dist as sdist
 from . import ops
-from .convstem import _bn_forward, _kpad, _pack_conv_weight, bn_bwd_sums
+from .convbn import _bn_relu_out, _conv_bn_bwd, _conv_bn_fwd
 from .engine import BF16_WEIGHTS, _wgrad, grad_target
 
 BF16 = torch.bfloat16
@@ -84,7 +83,8 @@ class AudioNTTFn(torch.autograd.Function):
         x = x.contiguous()
         C = w1.shape[0]
         train = mod.training
-        bn1, bn2 = mod.features[1], mod.features[6 if se else 5]
+        f = mod.features
+        k2 = 5 if se else 4                                    # the second conv block's index in `features`
 
         def se_gate(p, L, wa, wb):
             """SE_Block.forward (model.py:207-211) on the pooled map p [B * L, C]: returns the gated map and what the backward needs."""
@@ -94,19 +94,9 @@ class AudioNTTFn(torch.autograd.Function):
             ops.se_fwd(p, B, L, C, wa.detach().contiguous(), wb.detach().contiguous(), s_, h_, e_, y)
             return y, (p, s_, h_, e_)
 
-        def bn_relu(h, bn, gamma, beta):
-            if train:
-                mean, rstd = _bn_forward(h, h.shape[0], bn)
-            else:                                              # eval: running statistics (the HEAR / linear-probe path)
-                mean, rstd = bn.running_mean.detach(), torch.rsqrt(bn.running_var.detach() + bn.eps)
-            a = torch.empty(h.shape, dtype=BF16, device=dev)
-            ops.bn_apply(h, mean, rstd, gamma.detach(), beta.detach(), True, y_bf16=a)
-            return a, mean, rstd
-
-        # block 1: direct conv (C_in = 1) -> BN + ReLU -> pool
-        h1 = torch.empty(B * H * W, C, device=dev)
-        ops.conv3x3_c1_fwd(x, w1.detach().reshape(C, 9).contiguous(), b1.detach(), (1, 1), h1)
-        a1, m1, r1 = bn_relu(h1, bn1, g1, be1)
+        # block 1: direct conv (C_in = 1, + bias) -> BN + ReLU -> pool
+        r1 = _conv_bn_fwd(f[0], f[1], None, B, H, W, 1, True, x_img=x, training=train)
+        a1 = _bn_relu_out(r1)
         H2, W2 = H // 2, W // 2
         p1 = torch.empty(B * H2 * W2, C, dtype=BF16, device=dev); i1 = torch.empty(B * H2 * W2, C, dtype=torch.uint8, device=dev)
         ops.maxpool2_fwd(a1, B, H, W, C, p1, i1)
@@ -114,14 +104,9 @@ class AudioNTTFn(torch.autograd.Function):
         se_saved = [None, None]
         if se:
             p1, se_saved[0] = se_gate(p1, H2 * W2, se[0], se[1])
-        # block 2: im2col GEMM -> BN + ReLU -> pool
-        kp = _kpad(C)
-        P = torch.empty(B * H2 * W2, kp, dtype=BF16, device=dev)
-        ops.im2col3x3(p1, B, H2, W2, C, (1, 1), P)
-        h2 = torch.empty(B * H2 * W2, C, device=dev)
-        ops.gemm(P, _pack_conv_weight(w2, kp), bias=b2.detach(), out_f32=h2)
-        del P
-        a2, m2, r2 = bn_relu(h2, bn2, g2, be2)
+        # block 2: im2col GEMM (+ bias) on the pooled (gated) map -> BN + ReLU -> pool
+        r2 = _conv_bn_fwd(f[k2], f[k2 + 1], p1, B, H2, W2, C, True, training=train)
+        a2 = _bn_relu_out(r2)
         H4, W4 = H2 // 2, W2 // 2
         p2 = torch.empty(B * H4 * W4, C, dtype=BF16, device=dev); i2 = torch.empty(B * H4 * W4, C, dtype=torch.uint8, device=dev)
         ops.maxpool2_fwd(a2, B, H2, W2, C, p2, i2)
@@ -145,29 +130,28 @@ class AudioNTTFn(torch.autograd.Function):
         out = torch.empty(B, conv_d + dfc, device=dev)
         arg = torch.empty(B, conv_d + dfc, dtype=torch.int32, device=dev)
         ops.meanmax_time_fwd(stack.view(B, W4, conv_d + dfc), out, arg)
-        ctx.saved = (x, h1, m1, r1, p1, i1, h2, m2, r2, i2, X, h3, a3, h4, arg, keep, scale)
+        ctx.saved = (r1, i1, r2, i2, X, h3, a3, h4, arg, keep, scale)
         ctx.dims = (B, H, W, C, conv_d, hid, dfc)
-        ctx.params = (w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, w4, b4)
+        ctx.params = (w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, w4, b4, *se)
         ctx.se, ctx.se_saved = se, se_saved
-        ctx.train = train
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, h1, m1, r1, p1, i1, h2, m2, r2, i2, X, h3, a3, h4, arg, keep, scale = ctx.saved
+        r1, i1, r2, i2, X, h3, a3, h4, arg, keep, scale = ctx.saved
         B, H, W, C, conv_d, hid, dfc = ctx.dims
-        w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, w4, b4 = ctx.params
-        dev = x.device
+        w3, b3, w4, b4 = ctx.params[8:12]
+        dev = dout.device
         H2, W2, H4, W4 = H // 2, W // 2, H // 4, W // 4
         M = B * W4
-        Wn = sdist.get_world_size()
+        grads = {}
         dstack = torch.empty(B, W4, conv_d + dfc, device=dev)
         ops.meanmax_time_bwd(dout.contiguous().float(), arg, dstack)
         dstack = dstack.view(M, conv_d + dfc)
         # fc2 (+ ReLU)
         g4 = torch.empty(M, dfc, dtype=BF16, device=dev)
         ops.relu_mask_bwd(dstack[:, conv_d:], h4, None, 1.0, g4)
-        dw4b, dw4 = grad_target(w4); db4b, db4 = grad_target(b4)
+        dw4b, grads[id(w4)] = grad_target(w4); db4b, grads[id(b4)] = grad_target(b4)
         _wgrad(g4, a3, dw4b)
         ops.colsum_bf16(g4, db4b, accumulate=True)
         da3 = torch.empty(M, hid, device=dev)
@@ -175,7 +159,7 @@ class AudioNTTFn(torch.autograd.Function):
         # dropout + ReLU + fc1
         g3 = torch.empty(M, hid, dtype=BF16, device=dev)
         ops.relu_mask_bwd(da3, h3, keep, scale, g3)
-        dw3b, dw3 = grad_target(w3); db3b, db3 = grad_target(b3)
+        dw3b, grads[id(w3)] = grad_target(w3); db3b, grads[id(b3)] = grad_target(b3)
         _wgrad(g3, X, dw3b)
         ops.colsum_bf16(g3, db3b, accumulate=True)
         dX = torch.empty(M, conv_d, device=dev)
@@ -183,51 +167,24 @@ class AudioNTTFn(torch.autograd.Function):
         # frames (MLP input + the stacked copy) -> pooled map -> pool / BN / conv 2
         dp2 = torch.empty(B * H4 * W4, C, device=dev)
         ops.frames_to_nhwc(dX, dstack[:, :conv_d], B, H4, W4, C, dp2)
-        se, dse = ctx.se, [None] * 4
+        se = ctx.se
 
-        def se_gate_bwd(dy, saved, wa, wb, L, slot):
+        def se_gate_bwd(dy, saved, wa, wb, L):
             """dy fp32 [B * L, C] at the gate's output -> gradient at its input; W1 / W2 gradients accumulated into their targets."""
             p_in, s_, h_, e_ = saved
             dx_ = torch.empty_like(dy)
-            dab, dse[slot] = grad_target(wa); dbb, dse[slot + 1] = grad_target(wb)
+            dab, grads[id(wa)] = grad_target(wa); dbb, grads[id(wb)] = grad_target(wb)
             ops.se_bwd(dy, p_in, B, L, C, wa.detach().contiguous(), wb.detach().contiguous(), s_, h_, e_, dx_, dab, dbb)
             return dx_
 
         if se:
-            dp2 = se_gate_bwd(dp2, ctx.se_saved[1], se[2], se[3], H4 * W4, 2)
+            dp2 = se_gate_bwd(dp2, ctx.se_saved[1], se[2], se[3], H4 * W4)
         da2 = torch.empty(B * H2 * W2, C, device=dev)
         ops.maxpool2_bwd(dp2, i2, B, H2, W2, C, da2)
-
-        def bn_bwd(da, h, mean, rstd, gamma, beta, rows):
-            s = torch.empty(2, C, device=dev)
-            ops.bn_bwd_stats_tall(da, h, mean, rstd, gamma, beta, True, s[0], s[1])
-            dgb, dg = grad_target(gamma); dbb, dbt = grad_target(beta)
-            ops.axpy(dbb, s[0]); ops.axpy(dgb, s[1])
-            s = bn_bwd_sums(s, ctx.train)
-            dh = torch.empty(rows, C, dtype=BF16, device=dev)
-            ops.bn_bwd_apply(da, h, mean, rstd, gamma, beta, True, s[0], s[1], 1.0 / (rows * Wn), dx_bf16=dh)
-            return dh, dg, dbt
-
-        dh2, dg2, dbe2 = bn_bwd(da2, h2, m2, r2, g2, be2, B * H2 * W2)
-        kp = _kpad(C)
-        P = torch.empty(B * H2 * W2, kp, dtype=BF16, device=dev)
-        ops.im2col3x3(p1, B, H2, W2, C, (1, 1), P)
-        dwp = torch.zeros(C, kp, device=dev)
-        _wgrad(dh2, P, dwp)
-        del P
-        dw2b, dw2 = grad_target(w2); db2b, db2 = grad_target(b2)
-        ops.axpy(dw2b.view(-1), dwp[:, :9 * C].reshape(C, 3, 3, C).permute(0, 3, 1, 2).contiguous().view(-1))
-        ops.colsum_bf16(dh2, db2b, accumulate=True)
-        dP = torch.empty(B * H2 * W2, kp, dtype=BF16, device=dev)
-        ops.gemm(dh2, _pack_conv_weight(w2, kp), b_kmajor=False, out_bf16=dP)
-        dp1 = torch.empty(B * H2 * W2, C, device=dev)
-        ops.col2im3x3(dP, B, H2, W2, C, (1, 1), dp1)
-        del dP
+        dp1 = _conv_bn_bwd(r2, da2, grads)
         if se:
-            dp1 = se_gate_bwd(dp1, ctx.se_saved[0], se[0], se[1], H2 * W2, 0)
+            dp1 = se_gate_bwd(dp1, ctx.se_saved[0], se[0], se[1], H2 * W2)
         da1 = torch.empty(B * H * W, C, device=dev)
         ops.maxpool2_bwd(dp1, i1, B, H, W, C, da1)
-        dh1, dg1, dbe1 = bn_bwd(da1, h1, m1, r1, g1, be1, B * H * W)
-        dw1b, dw1 = grad_target(w1); db1b, db1 = grad_target(b1)
-        ops.conv3x3_c1_wgrad(x, dh1, (1, 1), dw1b.view(C, 9), db1b)
-        return (None, None, None, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2, dw3, db3, dw4, db4) + (tuple(dse) if se else ())
+        _conv_bn_bwd(r1, da1, grads)
+        return (None, None, None) + tuple(grads[id(p)] for p in ctx.params)

@@ -219,21 +219,48 @@ def _gemm_f32_long_k(A16, W16, out, b_kmajor=True):
         ops.gemm(A16, W16, b_kmajor=b_kmajor, out_f32=out)
 
 
+def _linear_bn_front(x, w0, running_mean, running_var):
+    """The projector blocks' front: x -> (x16 = bf16(x), h = x16 W0^T fp32, BatchNorm1d batch mean, rstd)."""
+    x16 = ops.cast_bf16(x.contiguous())
+    h = torch.empty(x.shape[0], w0.shape[0], device=x.device)
+    ops.gemm(x16, BF16_WEIGHTS.get(w0), out_f32=h)
+    mean, rstd = _bn_forward_stats(h, BN_EPS, running_mean, running_var)
+    return x16, h, mean, rstd
+
+
+def _linear_bn_bwd(da, x16, h, mean, rstd, w0, gamma, beta, need_dx):
+    """The projector blocks' tail: da fp32 at the ReLU output -> (dx, dW0, dgamma, dbeta).  BatchNorm1d backward with its sums summed
+    over ranks, then the first Linear's weight and input gradients."""
+    B, Hd = h.shape
+    dev = h.device
+    s = torch.empty(2, Hd, device=dev)
+    ops.bn_bwd_stats(da, h, mean, rstd, gamma, beta, True, s[0], s[1])
+    dgb, dgamma = grad_target(gamma)                    # local contributions (summed over ranks with the other grads)
+    dbb, dbeta = grad_target(beta)
+    ops.axpy(dbb, s[0])
+    ops.axpy(dgb, s[1])
+    sdist.all_reduce_sum_(s)
+    dh = torch.empty(B, Hd, dtype=BF16, device=dev)
+    ops.bn_bwd_apply(da, h, mean, rstd, gamma, beta, True, s[0], s[1], 1.0 / (B * sdist.get_world_size()), dx_bf16=dh)
+    dw0b, dw0 = grad_target(w0)
+    _wgrad(dh, x16, dw0b)
+    dx = None
+    if need_dx:
+        dx = torch.empty(B, w0.shape[1], device=dev)
+        _gemm_f32_long_k(dh, BF16_WEIGHTS.get(w0), dx, b_kmajor=False)
+    return dx, dw0, dgamma, dbeta
+
+
 class MlpBnReluFn(torch.autograd.Function):
     """One crop chunk through Linear(nb) -> BN1d(train, affine) -> ReLU -> Linear(nb)  (model.py:16-23,39-45).
     With a process group the BN is a SyncBN over the global chunk (utils/utils.py:411)."""
 
     @staticmethod
     def forward(ctx, x, w0, gamma, beta, w1, running_mean, running_var):
-        B = x.shape[0]
-        dev = x.device
-        x16 = ops.cast_bf16(x.contiguous())
-        h = torch.empty(B, w0.shape[0], device=dev)
-        ops.gemm(x16, BF16_WEIGHTS.get(w0), out_f32=h)
-        mean, rstd = _bn_forward_stats(h, BN_EPS, running_mean, running_var)
-        a = torch.empty(B, w0.shape[0], dtype=BF16, device=dev)
+        x16, h, mean, rstd = _linear_bn_front(x, w0, running_mean, running_var)
+        a = torch.empty(h.shape, dtype=BF16, device=h.device)
         ops.bn_apply(h, mean, rstd, gamma.detach(), beta.detach(), True, y_bf16=a)
-        z = torch.empty(B, w1.shape[0], device=dev)
+        z = torch.empty(h.shape[0], w1.shape[0], device=h.device)
         _gemm_f32_long_k(a, BF16_WEIGHTS.get(w1), z)
         ctx.save_for_backward(x16, h, mean, rstd, a, w0, gamma, beta, w1)
         return z
@@ -241,29 +268,12 @@ class MlpBnReluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dz):
         x16, h, mean, rstd, a, w0, gamma, beta, w1 = ctx.saved_tensors
-        B, Hd = h.shape
-        dev = h.device
-        W = sdist.get_world_size()
         dz16 = ops.cast_bf16(dz.contiguous())
         dw1b, dw1 = grad_target(w1)
         _wgrad(dz16, a, dw1b)
-        da = torch.empty(B, Hd, device=dev)      # fp32: BN backward subtracts batch means, keep its input unrounded
+        da = torch.empty(h.shape, device=h.device)      # fp32: BN backward subtracts batch means, keep its input unrounded
         ops.gemm(dz16, BF16_WEIGHTS.get(w1), b_kmajor=False, out_f32=da)
-        s = torch.empty(2, Hd, device=dev)
-        ops.bn_bwd_stats(da, h, mean, rstd, gamma, beta, True, s[0], s[1])
-        dgb, dgamma = grad_target(gamma)                    # local contributions (summed over ranks with the other grads)
-        dbb, dbeta = grad_target(beta)
-        ops.axpy(dbb, s[0])
-        ops.axpy(dgb, s[1])
-        sdist.all_reduce_sum_(s)
-        dh = torch.empty(B, Hd, dtype=BF16, device=dev)
-        ops.bn_bwd_apply(da, h, mean, rstd, gamma, beta, True, s[0], s[1], 1.0 / (B * W), dx_bf16=dh)
-        dw0b, dw0 = grad_target(w0)
-        _wgrad(dh, x16, dw0b)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(B, w0.shape[1], device=dev)
-            _gemm_f32_long_k(dh, BF16_WEIGHTS.get(w0), dx, b_kmajor=False)
+        dx, dw0, dgamma, dbeta = _linear_bn_bwd(da, x16, h, mean, rstd, w0, gamma, beta, ctx.needs_input_grad[0])
         return dx, dw0, dgamma, dbeta, dw1, None, None
 
 
@@ -273,13 +283,8 @@ class LinearBnReluFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w0, gamma, beta, running_mean, running_var):
-        B = x.shape[0]
-        dev = x.device
-        x16 = ops.cast_bf16(x.contiguous())
-        h = torch.empty(B, w0.shape[0], device=dev)
-        ops.gemm(x16, BF16_WEIGHTS.get(w0), out_f32=h)
-        mean, rstd = _bn_forward_stats(h, BN_EPS, running_mean, running_var)
-        a = torch.empty(B, w0.shape[0], device=dev)
+        x16, h, mean, rstd = _linear_bn_front(x, w0, running_mean, running_var)
+        a = torch.empty(h.shape, device=h.device)
         ops.bn_apply(h, mean, rstd, gamma.detach(), beta.detach(), True, y_f32=a)
         ctx.save_for_backward(x16, h, mean, rstd, w0, gamma, beta)
         return a
@@ -287,25 +292,7 @@ class LinearBnReluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, da):
         x16, h, mean, rstd, w0, gamma, beta = ctx.saved_tensors
-        B, Hd = h.shape
-        dev = h.device
-        W = sdist.get_world_size()
-        da = da.contiguous().float()
-        s = torch.empty(2, Hd, device=dev)
-        ops.bn_bwd_stats(da, h, mean, rstd, gamma, beta, True, s[0], s[1])
-        dgb, dgamma = grad_target(gamma)                    # local contributions (summed over ranks with the other grads)
-        dbb, dbeta = grad_target(beta)
-        ops.axpy(dbb, s[0])
-        ops.axpy(dgb, s[1])
-        sdist.all_reduce_sum_(s)
-        dh = torch.empty(B, Hd, dtype=BF16, device=dev)
-        ops.bn_bwd_apply(da, h, mean, rstd, gamma, beta, True, s[0], s[1], 1.0 / (B * W), dx_bf16=dh)
-        dw0b, dw0 = grad_target(w0)
-        _wgrad(dh, x16, dw0b)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(B, w0.shape[1], device=dev)
-            _gemm_f32_long_k(dh, BF16_WEIGHTS.get(w0), dx, b_kmajor=False)
+        dx, dw0, dgamma, dbeta = _linear_bn_bwd(da.contiguous().float(), x16, h, mean, rstd, w0, gamma, beta, ctx.needs_input_grad[0])
         return dx, dw0, dgamma, dbeta, None, None
 
 

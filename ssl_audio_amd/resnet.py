@@ -14,10 +14,8 @@ BatchNorm2d statistics are exchanged across data-parallel ranks like the project
 import torch
 import torch.nn as nn
 
-from . import dist as sdist
 from . import ops
-from .convstem import BN_EPS, BN_MOMENTUM, _bn_forward, _kpad, _pack_conv_weight, bn_bwd_sums
-from .engine import BF16_WEIGHTS, _wgrad, grad_target
+from .convbn import _bn_relu_out, _conv_bn_bwd, _conv_bn_fwd
 
 BF16 = torch.bfloat16
 
@@ -106,111 +104,6 @@ def resnet18_ReGP_NRF():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-class _ConvBN:
-    """One convolution + BatchNorm2d of the forward, with what its backward needs."""
-    __slots__ = ("conv", "bn", "k", "stride", "relu", "S", "H", "W", "Ci", "Ho", "Wo", "Co", "a_in", "x_img", "h", "mean", "rstd", "train")
-
-
-def _conv_bn_fwd(conv, bn, a16, S, H, W, Ci, relu, x_img=None, training=True):
-    """a16 bf16 [S*H*W, Ci] (or x_img fp32 [S,1,H,W] for the single-channel first layer) -> record with h = conv output (fp32) and the
-    batch statistics.  3x3 (pad 1) through im2col + GEMM, 1x1 through row subsampling + GEMM."""
-    r = _ConvBN()
-    r.conv, r.bn, r.relu = conv, bn, relu
-    r.k = conv.kernel_size[0]
-    r.stride = _pair(conv.stride)
-    r.S, r.H, r.W, r.Ci = S, H, W, Ci
-    sh, sw = r.stride
-    r.Co = conv.weight.shape[0]
-    dev = conv.weight.device
-    if r.k == 3:
-        r.Ho, r.Wo = ops.conv_out_size(H, sh), ops.conv_out_size(W, sw)
-    else:
-        r.Ho, r.Wo = (H - 1) // sh + 1, (W - 1) // sw + 1
-    M = S * r.Ho * r.Wo
-    r.h = torch.empty(M, r.Co, device=dev)
-    r.x_img, r.a_in = x_img, a16
-    if x_img is not None:
-        ops.conv3x3_c1_fwd(x_img, conv.weight.detach().reshape(r.Co, 9).contiguous(), None, r.stride, r.h)
-    elif r.k == 3:
-        kp = _kpad(Ci)
-        P = torch.empty(M, kp, dtype=BF16, device=dev)
-        ops.im2col3x3(a16, S, H, W, Ci, r.stride, P)
-        ops.gemm(P, _pack_conv_weight(conv.weight, kp), out_f32=r.h)
-        del P
-    else:
-        xs = a16
-        if r.stride != (1, 1):
-            xs = torch.empty(M, Ci, dtype=BF16, device=dev)
-            ops.subsample_fwd(a16, S, H, W, Ci, r.stride, xs)
-        r.a_in = xs                                              # the 1x1 convolution's GEMM operand (already subsampled)
-        ops.gemm(xs, BF16_WEIGHTS.get(conv.weight), out_f32=r.h)
-    r.train = training
-    r.mean, r.rstd = _bn_forward(r.h, M, bn, training)
-    return r
-
-
-def _conv_bn_bwd(r, dz, grads, dx_out=None, need_dx=True):
-    """dz fp32 [M, Co]: gradient at the BatchNorm output (after the ReLU when r.relu).  Accumulates the parameter gradients into `grads`
-    (id -> autograd value) and returns the gradient at the convolution's input: fp32 [S*H*W, Ci] written by col2im for a 3x3, or, for a
-    1x1, ADDED into dx_out at the sampled pixels."""
-    conv, bn = r.conv, r.bn
-    dev = dz.device
-    M, Co, Ci = r.h.shape[0], r.Co, r.Ci
-    W_ = sdist.get_world_size()
-    gamma, beta = bn.weight, bn.bias
-    s = torch.empty(2, Co, device=dev)
-    ops.bn_bwd_stats_tall(dz, r.h, r.mean, r.rstd, gamma, beta, r.relu, s[0], s[1])
-    dgb, grads[id(gamma)] = grad_target(gamma)
-    dbb, grads[id(beta)] = grad_target(beta)
-    ops.axpy(dbb, s[0])
-    ops.axpy(dgb, s[1])
-    s = bn_bwd_sums(s, r.train)
-    cpad = (Co + 63) // 64 * 64 if r.x_img is None else Co            # zero columns up to the dgrad GEMM's K granule
-    dh_full = torch.zeros(M, cpad, dtype=BF16, device=dev) if cpad != Co else torch.empty(M, Co, dtype=BF16, device=dev)
-    dh = dh_full[:, :Co]
-    ops.bn_bwd_apply(dz, r.h, r.mean, r.rstd, gamma, beta, r.relu, s[0], s[1], 1.0 / (M * W_), dx_bf16=dh)
-    dwbuf, grads[id(conv.weight)] = grad_target(conv.weight)
-    if r.x_img is not None:
-        ops.conv3x3_c1_wgrad(r.x_img, dh, r.stride, dwbuf.view(Co, 9))
-        return None
-    if r.k == 1:
-        _wgrad(dh, r.a_in, dwbuf.view(Co, Ci))
-        if not need_dx:
-            return None
-        dxs = torch.empty(M, Ci, dtype=BF16, device=dev)
-        w16 = BF16_WEIGHTS.get(conv.weight)
-        if cpad != Co:
-            wp = torch.zeros(cpad, Ci, dtype=BF16, device=dev)
-            wp[:Co] = w16
-            w16 = wp
-        ops.gemm(dh_full, w16, b_kmajor=False, out_bf16=dxs)
-        if r.stride == (1, 1):
-            raise NotImplementedError("1x1 convolution without stride is not part of the BasicBlock networks")
-        ops.subsample_bwd_add(dxs, r.S, r.H, r.W, Ci, r.stride, dx_out)
-        return dx_out
-    kp = _kpad(Ci)
-    P = torch.empty(M, kp, dtype=BF16, device=dev)
-    ops.im2col3x3(r.a_in, r.S, r.H, r.W, Ci, r.stride, P)            # recomputed: cheaper than keeping 9x the activations
-    dwp = torch.zeros(Co, kp, device=dev)
-    _wgrad(dh, P, dwp)
-    del P
-    ops.axpy(dwbuf.view(-1), dwp[:, :9 * Ci].reshape(Co, 3, 3, Ci).permute(0, 3, 1, 2).contiguous().view(-1))
-    if not need_dx:
-        return None
-    dP = torch.empty(M, kp, dtype=BF16, device=dev)
-    ops.gemm(dh_full, _pack_conv_weight(conv.weight, kp, rows=cpad), b_kmajor=False, out_bf16=dP)
-    da = torch.empty(r.S * r.H * r.W, Ci, device=dev)
-    ops.col2im3x3(dP, r.S, r.H, r.W, Ci, r.stride, da)
-    return da
-
-
-def _bn_relu_out(r):
-    """BN (+ ReLU) of a record -> bf16 activation for the next convolution."""
-    a = torch.empty(r.h.shape[0], r.Co, dtype=BF16, device=r.h.device)
-    ops.bn_apply(r.h, r.mean, r.rstd, r.bn.weight.detach(), r.bn.bias.detach(), r.relu, y_bf16=a)
-    return a
-
-
 class ResNetFn(torch.autograd.Function):
     """x [S,1,F,T] fp32 -> embedding [S, 512] (average pool) or [S, C * F'] (ReGP).  Gradients: every parameter (the input gets none)."""
 

@@ -194,7 +194,7 @@ RESNET_KEYS = ["backbone.encoder.conv1.0.weight", "backbone.encoder.conv1.4.weig
 def _resnet_step(rank, world):
     """BASELINE config 1's network (ResNet-18 + projector) on the drop-in classes under model_setup_ddp: 20 BatchNorm2d layers whose
     statistics and backward sums are exchanged across ranks (SyncBN, utils/utils.py:411), convolution weight gradients summed by the
-    wrapper's hooks.  Same code path as the ConvStem / AudioNTT BatchNorms (convstem._bn_forward)."""
+    wrapper's hooks.  Same code path as the ConvStem / AudioNTT BatchNorms (convbn._bn_forward)."""
     from ssl_audio_amd import hyperparameters as hp, model, utils
     from ssl_audio_amd.loss import BarlowTwinsLoss
     dev = torch.device("cuda:0")
